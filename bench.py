@@ -1,6 +1,6 @@
 """bench.py — headline benchmark: audio clips/sec for one training step at 48 kHz, n_fft 1024.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of the hot path over one batch of synthetic VCTK-shaped clips resident in
@@ -10,9 +10,14 @@ the 41 M-parameter MPD, backward, AdamW for G and D — `configs/vm_asr_48k_MPD.
 reference as written (per-GPU batch 4, DIMS 16).  N GPUs = N processes, batch sharded by clip,
 DDP all-reduce over RCCL; value = N*B*K / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
-  roofline      dominant HIP kernel, timed live with HIP events on its launch stream
-  cpu_baseline  the same train step on the host cores with the CPU oracle kernels (rank 0, N=1)
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): the driver's contract.
+--dump-outputs DIR  after the timed steps, rank 0 writes what the last timed step returned and updated as DIR/<name>.npy
+                    (float32 / float64; see dump_outputs); the inputs are seeded and the last timed step starts from the
+                    seeded initial state, so the files are the same from run to run up to rounding
+--full              adds, after the timed steps, what takes runs of its own (the full record goes to --detail):
+  roofline          dominant HIP kernel, timed live with HIP events on its launch stream (eager passes of the same K steps)
+  operating_points  secondary configurations, each built, captured and timed in the same process (N=1)
+  cpu_baseline      the same train step on the host cores with the CPU oracle kernels (rank 0, N=1)
 """
 import argparse
 import json
@@ -136,9 +141,10 @@ def cpu_baseline(config, budget_s=40.0):
 RUN_INFO = {}       # of the last run_point(): the captured step's generator stream count and, if both variants were captured, their times
 
 
-def run_point(config, args, device, rank, world, steps, warmup, timing, with_metrics=False):
+def run_point(config, args, device, rank, world, steps, warmup, timing, with_metrics=False, dump_dir=None):
     """Build the trainer for `config`, warm up, capture, time `steps` steps (barrier + synchronize on both sides, max over
-    ranks) and — `timing` — run the same steps once more eagerly with the library's HIP-event timer on.
+    ranks), — `dump_dir` — write what the last timed step computed there (rank 0), and — `timing` — run the same steps once
+    more eagerly with the library's HIP-event timer on.
     -> (seconds for `steps` steps, graphed?, per-rank dict or None, {kernel: dict(launches, ms, alg_bytes)} or None)."""
     from vm_asr_amd import _lib
     trainer = build_trainer(config, device, amp=not args.no_amp, capturable=not args.no_graphs, amp_scope=args.amp_scope)
@@ -165,23 +171,42 @@ def run_point(config, args, device, rank, world, steps, warmup, timing, with_met
         mets = default_metric_ftns(config)
 
     def one_step():
-        out, _ = trainer.train_step(*batch)
+        res = trainer.train_step(*batch)
         for m in mets:
-            float(m(out.float().squeeze(1), batch[1].squeeze(1), hf=batch[2]))
+            float(m(res[0].float().squeeze(1), batch[1].squeeze(1), hf=batch[2]))
+        return res
+    # The last timed step starts again from the state the warm-up starts from: seeded weights and buffers, fresh optimiser moments
+    # (what enable_graphs leaves) and a re-seeded generator for DropPath.  The step's closing float atomics sum in whatever order the
+    # workgroups finish, and W + K - 1 AdamW updates on one batch compound those rounding differences into a different model, run
+    # to run; from one state, what the last step computes is a function of the inputs alone (--dump-outputs).  The restore runs with
+    # the clock stopped: every timed step is one full train step, as before.
+    start = trainer._snapshot_training_state()
     for _ in range(warmup):
         one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     trainer.time_reduces = world > 1
+    last = None
+    paused = 0.0
     t0 = time.perf_counter()
-    for _ in range(steps):
-        one_step()
+    for i in range(steps):
+        if i == steps - 1:
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            trainer._restore_training_state(start)
+            torch.manual_seed(config.SEED + 1 + rank)
+            torch.cuda.synchronize()
+            paused += time.perf_counter() - tp
+        last = one_step()
     torch.cuda.synchronize()
-    dt_own = time.perf_counter() - t0          # this rank's own time to finish its K steps
+    dt_own = time.perf_counter() - t0 - paused          # this rank's own time to finish its K steps
     if world > 1:
         dist.barrier()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
+    del start
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, trainer, last)      # (before the timing passes below run more steps)
     per_rank = None
     if world > 1:
         trainer.time_reduces = False
@@ -240,6 +265,42 @@ def run_point(config, args, device, rank, world, steps, warmup, timing, with_met
     del trainer
     torch.cuda.empty_cache()
     return dt, graphed, per_rank, prof
+
+
+DUMP_WAVE_MAX = 1 << 23         # float32 entries of the output wave written at most (whole clips, the first ones): 32 MB
+DUMP_PARAM_SAMPLE = 1 << 20     # float32 entries written of one model's updated weights at most: 4 MB
+
+
+def dump_outputs(path, trainer, last):
+    """--dump-outputs: what the last timed step computed, as the caller of `Trainer.train_step` receives it, in `path`/<name>.npy:
+      wave_out         the generator's output wave of that step, float32 (B, 1, T) (the first clips only above DUMP_WAVE_MAX)
+      loss_<name>      every loss of the step's log dict, float64 scalar (characters other than letters, digits, _-. of the key: _)
+      <model>_params   the model's weights after the step's AdamW update: every parameter flattened in `parameters()` order, float32;
+                       above DUMP_PARAM_SAMPLE entries, a fixed sample of them (indices drawn with seed 0, ascending).
+    The inputs are seeded and the last timed step starts from the seeded initial state (run_point), so two runs with the same
+    arguments differ only by what the rounding of ONE step's atomic sums makes of it: losses ~1e-7 relative, weights by at most
+    2 x lr (AdamW's first update turns a gradient at rounding level into +-lr), the output wave ~1e-3 relative on some clips
+    (measured at the headline workload); VMASR_DETERMINISTIC=1: bit-identical (a slower step)."""
+    import numpy as np
+    from vm_asr_amd.trainer import unwrap
+    assert last is not None, "--dump-outputs needs at least one timed step"
+    os.makedirs(path, exist_ok=True)
+    wave, logs = last
+    per_clip = max(1, wave[0].numel())
+    arrays = {"wave_out": wave[:max(1, DUMP_WAVE_MAX // per_clip)].detach().float().cpu().numpy()}
+    for k, v in sorted(logs.items()):       # (log keys such as "generator/adversarial_mpd": one file name each)
+        arrays["loss_" + "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in k)] = np.asarray(float(v), dtype=np.float64)
+    for name, m in trainer.models.items():
+        if m is None:
+            continue
+        flat = torch.cat([p.detach().float().reshape(-1) for p in unwrap(m).parameters()])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_PARAM_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[f"{name}_params"] = flat.cpu().numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    print(f"[bench] outputs of the last timed step: {', '.join(sorted(arrays))} -> {path}", file=sys.stderr, flush=True)
 
 
 SCAN_KERNELS = ("ss2d_fwd_agg", "ss2d_fwd_apply", "ss2d_bwd_agg", "ss2d_bwd_apply", "ss2d_carry", "ss2d_deep_fwd", "ss2d_deep_bwd")
@@ -383,10 +444,10 @@ def _pick(d, keys, nd=4):
 MAX_LINE = 3000      # the driver keeps an 8 000-character tail of stdout: the final line must fit with room to spare
 
 
-def compact(out):
+def compact(out, detail=True):
     """The driver's line: contract keys + `roofline`, `cpu_baseline`, `operating_points`, `distributed` reduced to their
     headline numbers (<= MAX_LINE characters for any world size).  Per-kernel tables, per-shape tables, notes and per-rank
-    device records are the DETAIL record (`bench_detail.json`), never part of this line."""
+    device records are the DETAIL record (`bench_detail.json`, --full), never part of this line; `detail`: name it."""
     c = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                              "vs_baseline", "dtype", "data") if k in out}
     c["value"], c["ms_per_step"] = _r(c["value"], 3), _r(c["ms_per_step"], 4)
@@ -432,7 +493,8 @@ def compact(out):
                             "allreduce_exposed_ms_per_step": (None if any(v is None for v in pr["allreduce_exposed_ms_per_step"])
                                                               else max(pr["allreduce_exposed_ms_per_step"])),
                             "collectives": str(pr.get("collectives", ""))[:40]}
-    c["detail"] = out.get("detail_file", "bench_detail.json")
+    if detail:
+        c["detail"] = out.get("detail_file", "bench_detail.json")
     line = json.dumps(c, separators=(",", ":"))
     if len(line) > MAX_LINE:        # never let an unforeseen field push the line out of the driver's tail again
         for k in ("operating_points", "distributed", "cpu_baseline"):
@@ -441,7 +503,7 @@ def compact(out):
             if k == "cpu_baseline" and k in c:
                 c[k] = _pick(c[k], ("value", "unit", "cores", "kind"))
             elif k in c:
-                c[k] = {"see": c["detail"]}
+                c[k] = {"see": c.get("detail")}
             line = json.dumps(c, separators=(",", ":"))
     assert len(line) <= MAX_LINE, len(line)
     return line
@@ -463,8 +525,14 @@ def emit(out, detail_path):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the HIP-event kernel timing passes (roofline), "
+                         "the secondary operating points and the CPU baseline (each can be left out with its --no-* option); the full "
+                         "record is written to --detail.  Off: set up, warm up, time the steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="where the full record (per-kernel / per-shape tables, notes, per-rank device records) is written; the "
+                    help="--full: where the full record (per-kernel / per-shape tables, notes, per-rank device records) is written; the "
                          "stdout line is the compact record only")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -490,6 +558,8 @@ def main():
                          "sharing the chip), a one-stream pass (every kernel alone on the chip: the `roofline` figures), or both (default)")
     ap.add_argument("--no-graphs", action="store_true", help="run the step eagerly instead of replaying HIP graphs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("VMASR_BENCH_WATCHDOG"):      # debugging aid: dump all stacks and exit if the run wedges
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["VMASR_BENCH_WATCHDOG"]), exit=True)
@@ -506,8 +576,9 @@ def main():
     config = make_config(args.workload, args.batch)
     from vm_asr_amd.trainer import distributed_info
     dinfo = distributed_info(device)
-    dt, graphed, per_rank, prof = run_point(config, args, device, rank, world, args.steps, args.warmup, not args.no_kernel_timing,
-                                            with_metrics=args.with_metrics)
+    dt, graphed, per_rank, prof = run_point(config, args, device, rank, world, args.steps, args.warmup,
+                                            args.full and not args.no_kernel_timing, with_metrics=args.with_metrics,
+                                            dump_dir=args.dump_outputs)
     main_info = dict(RUN_INFO)
     timing = prof is not None
 
@@ -603,7 +674,8 @@ def main():
                     "shapes": shape_table(shared_prof, dom),      # per call shape, beside `roofline.shapes` (alone on the chip)
                     "kernels": {k: {"launches": v["launches"], "avg_us": round(v["avg_us"], 2), "GB/s": round(v["gbs"], 1),
                                     "ms_per_step": round(v["ms"] / args.steps, 3)} for k, v in sorted(kern2.items())}}
-    if rank == 0 and world == 1 and not args.no_extra_points and args.workload == "vm_asr_48k_MPD" and not args.batch and not args.no_graphs:
+    if (args.full and rank == 0 and world == 1 and not args.no_extra_points and args.workload == "vm_asr_48k_MPD" and not args.batch
+            and not args.no_graphs):
         # driver-visible secondary operating points: the reference-precision discriminator GEMMs, and
         # configs[4]'s yaml (DIMS 32, batch 8) with its own roofline block.  Never part of `value`.
         pts = {}
@@ -620,14 +692,16 @@ def main():
                 pts[name] = {"error": f"{type(e).__name__}: {e}"}
                 torch.cuda.empty_cache()
         out["operating_points"] = pts
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(config)
         except Exception as e:  # the baseline is informative; never lose the GPU number over it
             out["cpu_baseline"] = {"value": None, "unit": "clips/s", "cores": os.cpu_count(), "kind": "port",
                                    "sample": f"failed: {type(e).__name__}: {e}"}
-    if rank == 0:
+    if rank == 0 and args.full:
         emit(out, args.detail)
+    elif rank == 0:
+        print(compact(out, detail=False), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -87,3 +87,28 @@ def test_compact_line_with_in_graph_collectives():
     rec = json.loads(bench.compact(out))
     assert rec["distributed"]["allreduce_exposed_ms_per_step"] is None and rec["distributed"]["collectives"].startswith("branches of the step")
     assert len(bench.compact(out)) <= bench.MAX_LINE
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path, monkeypatch):
+    """--dump-outputs: the step's output wave, its losses (one file per log key) and the updated weights (a fixed sample above
+    DUMP_PARAM_SAMPLE entries), float32 / float64, the same sample on every run."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 100)
+
+    class _Trainer:
+        models = {"generator": torch.nn.Linear(4, 3), "mpd": torch.nn.Linear(20, 10)}
+    wave = torch.randn(2, 1, 50)
+    logs = {"total_loss": torch.tensor(1.5), "generator/adversarial_mpd": torch.tensor(0.25)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), _Trainer, (wave, logs))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["generator_params.npy", "loss_generator_adversarial_mpd.npy", "loss_total_loss.npy", "mpd_params.npy", "wave_out.npy"]
+    got = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert got["wave_out.npy"].dtype == np.float32 and np.array_equal(got["wave_out.npy"], wave.numpy())
+    assert got["loss_generator_adversarial_mpd.npy"].dtype == np.float64 and float(got["loss_generator_adversarial_mpd.npy"]) == 0.25
+    g = _Trainer.models["generator"]
+    assert np.array_equal(got["generator_params.npy"], torch.cat([g.weight.reshape(-1), g.bias]).detach().numpy())    # 15 <= 100: all
+    assert got["mpd_params.npy"].shape == (100,) and got["mpd_params.npy"].dtype == np.float32
+    for n in names:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / n)), n

@@ -1,16 +1,16 @@
 """The reference's configs/vm_asr_*.yaml drop in unchanged (north_star): every shipped yaml loads through
-vm_asr_amd.config.get_config and builds the models it names.  The yaml files are the reference's own and
-are read from the reference checkout — present in the build container, absent on the GPU box (skipped)."""
+vm_asr_amd.config.get_config and builds the models it names.  The yaml files are the reference's own, unmodified,
+kept as settings fixtures in tests/golden/configs/."""
 import glob
 import os
 
 import pytest
 
-REF_CONFIGS = "/root/reference/configs"
+REF_CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "configs")
 YAMLS = sorted(glob.glob(os.path.join(REF_CONFIGS, "vm_asr_*.yaml")))
+assert len(YAMLS) == 13, f"settings fixtures missing from {REF_CONFIGS}"
 
 
-@pytest.mark.skipif(not YAMLS, reason="reference checkout not present")
 @pytest.mark.parametrize("path", YAMLS, ids=[os.path.basename(p)[:-5] for p in YAMLS])
 def test_reference_yaml_loads_and_builds(path):
     import vm_asr_amd

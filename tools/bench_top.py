@@ -1,4 +1,4 @@
-"""Top kernels of the last bench.py run (bench_detail.json): dev tool.   python tools/bench_top.py [n] [path]"""
+"""Top kernels of the last `bench.py --full` run (bench_detail.json): dev tool.   python tools/bench_top.py [n] [path]"""
 import json
 import sys
 
