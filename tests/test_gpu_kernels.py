@@ -725,10 +725,9 @@ def test_skinny_linear_matches_float64(rows, K, N, dt):
 
 
 @pytest.mark.gpu
-def test_linear_takes_the_skinny_kernel_under_autocast_with_the_same_gradients():
+def test_linear_takes_the_skinny_kernel_under_autocast_with_the_same_gradients(monkeypatch):
     """vm_asr_amd.linear.linear on (B, H, W, C) activations with many rows: same output and gradients as F.linear in float64, at bf16
     tolerance; VMASR_SKINNY=0 gives the GEMM path."""
-    import os
     from vm_asr_amd import linear as L
     dev = torch.device("cuda:0")
     g = torch.Generator(device="cpu").manual_seed(4)
@@ -738,16 +737,13 @@ def test_linear_takes_the_skinny_kernel_under_autocast_with_the_same_gradients()
     gy = torch.randn(4, 256, 256, 12, generator=g).to(dev)
     res = {}
     for flag in ("1", "0"):
-        os.environ["VMASR_SKINNY"] = flag
-        try:
-            for t in (x, w, b):
-                t.grad = None
-            with torch.autocast("cuda", dtype=torch.bfloat16):
-                y = L.linear(x, w, b)
-            y.float().backward(gy)
-            res[flag] = (y.detach().float(), x.grad.clone(), w.grad.clone(), b.grad.clone())
-        finally:
-            os.environ.pop("VMASR_SKINNY", None)
+        monkeypatch.setenv("VMASR_SKINNY", flag)
+        for t in (x, w, b):
+            t.grad = None
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            y = L.linear(x, w, b)
+        y.float().backward(gy)
+        res[flag] = (y.detach().float(), x.grad.clone(), w.grad.clone(), b.grad.clone())
     x64, w64, b64 = x.detach().double().requires_grad_(True), w.detach().double().requires_grad_(True), b.detach().double().requires_grad_(True)
     y64 = torch.nn.functional.linear(x64, w64, b64)
     y64.backward(gy.double())

@@ -75,7 +75,7 @@ def test_fused_mlp_matches_float64_as_well_as_torch_autocast(d, shape, use_scale
 
 
 @pytest.mark.gpu
-def test_vssblock_uses_the_fused_mlp_under_autocast_only():
+def test_vssblock_uses_the_fused_mlp_under_autocast_only(monkeypatch):
     """Under bf16 autocast VSSBlock runs its Mlp branch through the fused kernel (same result as the unfused module path
     within bf16 accuracy); in fp32 it does not (the fused kernel is a bf16 operator)."""
     from vm_asr_amd import mlp as M
@@ -87,12 +87,8 @@ def test_vssblock_uses_the_fused_mlp_under_autocast_only():
     with torch.autocast("cuda", dtype=torch.bfloat16):
         assert M.supported(x, blk.norm2, blk.mlp)
         y1 = blk(x)
-        import os
-        os.environ["VMASR_FUSED_MLP"] = "0"
-        try:
-            y0 = blk(x)
-        finally:
-            os.environ.pop("VMASR_FUSED_MLP")
+        monkeypatch.setenv("VMASR_FUSED_MLP", "0")
+        y0 = blk(x)
     assert y1.dtype == torch.float32 and (y1 - y0).abs().max() <= 2e-2 * y0.abs().max()
 
 

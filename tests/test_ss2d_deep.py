@@ -133,10 +133,9 @@ def test_deep_core_bf16_activations():
 
 
 @pytest.mark.gpu
-def test_ss2d_module_uses_deep_core():
+def test_ss2d_module_uses_deep_core(monkeypatch):
     """SS2D.forward of a deep-stage block (d_model 64 -> d_inner 128, dt_rank 4, 32 x 32) runs the deep core and agrees with
     the unfused path (VMASR_SS2D_DEEP=0) on the same weights: output and every gradient."""
-    import os
     from vm_asr_amd import ss2d_deep
     from vm_asr_amd.vmamba import SS2D
     torch.manual_seed(0)
@@ -149,18 +148,14 @@ def test_ss2d_module_uses_deep_core():
         calls.append(a[0].shape)
         return orig(*a)
     out = []
+    monkeypatch.setattr(ss2d_deep, "ss2d_deep", spy)
     for flag in ("1", "0"):
-        os.environ["VMASR_SS2D_DEEP"] = flag
-        try:
-            ss2d_deep.ss2d_deep = spy
-            xi = x.clone().requires_grad_()
-            m.zero_grad()
-            y = m(xi)
-            y.square().mean().backward()
-            out.append([y.detach(), xi.grad] + [p.grad.clone() for p in m.parameters()])
-        finally:
-            ss2d_deep.ss2d_deep = orig
-            os.environ.pop("VMASR_SS2D_DEEP", None)
+        monkeypatch.setenv("VMASR_SS2D_DEEP", flag)
+        xi = x.clone().requires_grad_()
+        m.zero_grad()
+        y = m(xi)
+        y.square().mean().backward()
+        out.append([y.detach(), xi.grad] + [p.grad.clone() for p in m.parameters()])
     assert calls == [torch.Size([2, 128, 32, 32])]
     for a, b in zip(*out):
         err, scale = (a - b).abs().max().item(), max(b.abs().max().item(), 1e-12)

@@ -6,8 +6,10 @@ Missing library == hard error; there is deliberately no fallback path.
 import ctypes
 import os
 
+from . import knobs
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VMASR_LIB") or os.path.join(_HERE, "libvmasr_hip.so")   # VMASR_LIB: A/B builds (dev)
+LIB_PATH = knobs.get("VMASR_LIB") or os.path.join(_HERE, "libvmasr_hip.so")   # VMASR_LIB: A/B builds (dev)
 
 c_i32, c_i64, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
 
@@ -219,8 +221,9 @@ def lib():
             fn.restype, fn.argtypes = res, args
         if l.vmasr_abi_version() != 1:
             raise RuntimeError("libvmasr_hip.so ABI version mismatch")
-        if os.environ.get("VMASR_DETERMINISTIC", "0") == "1":
+        if knobs.get("VMASR_DETERMINISTIC"):
             l.vmasr_set_deterministic(1)
+        knobs.warn_undeclared()
         _lib = l
     return _lib
 
@@ -244,7 +247,7 @@ def det_mode():
     (vmasr_set_deterministic: what the tests and embedding programs use).  Every stream-layout decision (trainer._two_streams,
     model._lanes, enable_graphs' variants, bench.py's labels) asks HERE — the ordered-accumulation tickets are per kernel id, not
     per stream (csrc/common.h), so the mode keeps the one-stream layout however it was switched on."""
-    if os.environ.get("VMASR_DETERMINISTIC", "0") == "1":
+    if knobs.get("VMASR_DETERMINISTIC"):
         return True
     try:
         return bool(lib().vmasr_get_deterministic())
@@ -255,6 +258,38 @@ def det_mode():
 def current_stream(device):
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    """Device pointer of tensor `t` as a C ABI argument; None passes through (an absent optional operand)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def require_cuda(name, *tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError(f"{name}: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+
+
+def bf16_autocast():
+    import torch
+    return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
+def autocast_dtype(x):
+    """The dtype an autocast GEMM computes `x` in: the autocast dtype when autocast is on, else x's own."""
+    import torch
+    return torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+
+
+def f32c(t, shape):
+    """A parameter as the contiguous fp32 array of `shape` the kernels read."""
+    return t.detach().float().reshape(shape).contiguous()
+
+
+def rows2d(t, width):
+    """`t` as a (rows, width) matrix; a copy only when that view is not contiguous."""
+    t2 = t.reshape(-1, width)
+    return t2 if t2.is_contiguous() else t2.contiguous()
 
 
 K_COUNT = 60

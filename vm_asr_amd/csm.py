@@ -8,23 +8,18 @@ semantics of the PyTorch `CrossScan` / `CrossMerge` (model/vmamba.py:27-73):
 Each forward is the other's backward; both call `.contiguous()` on their input like the
 Triton versions do.  Compute: vm_asr_amd/csrc/csm.hip.  No CPU fallback.
 """
-import ctypes
 
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 __all__ = ["cross_scan", "cross_merge", "CrossScan", "CrossMerge", "CrossScanHIP", "CrossMergeHIP", "CrossScanF32"]
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def cross_scan(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
     """out_dtype: None = x.dtype; torch.float32 converts 16-bit activations on the fly."""
-    if not x.is_cuda:
-        raise RuntimeError("cross_scan: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("cross_scan", x)
     B, C, H, W = x.shape
     x = x.contiguous()
     out_dtype = out_dtype or x.dtype
@@ -38,8 +33,7 @@ def cross_scan(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
 
 def cross_merge(ys: torch.Tensor, H: int, W: int, out_dtype=None) -> torch.Tensor:
     """ys (B,4,C,H*W) or (B,4,C,H,W) -> (B,C,H*W); out_dtype 16-bit converts fp32 streams on the fly."""
-    if not ys.is_cuda:
-        raise RuntimeError("cross_merge: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("cross_merge", ys)
     B, K, C = ys.shape[:3]
     if K != 4:
         raise RuntimeError("cross_merge: expected 4 scan directions")

@@ -690,13 +690,23 @@ int cg_launch_cfg(CgParams &P, int epi, hipStream_t st, int kid, double bytes) {
     return check_launch("conv_mfma");
 }
 
+// tuning overrides shared by the forward / dgrad and the wgrad launchers, read once per process
+int env_conv_tile() {
+    static const int v = [] { const char *e = getenv("VMASR_CONV_TILE"); return e ? atoi(e) : 0; }();
+    return v;
+}
+int env_conv_mfma() {
+    static const int v = [] { const char *e = getenv("VMASR_CONV_MFMA"); return e ? atoi(e) : 16; }();
+    return v;
+}
+
 // 256 x 256 tiles when the output width allows and there are enough of them to fill the chip; VMASR_CONV_TILE=128 forces the small tile
 int cg_launch(CgParams &P, int epi, hipStream_t st, int kid, double bytes) {
-    static const int forced = [] { const char *e = getenv("VMASR_CONV_TILE"); return e ? atoi(e) : 0; }();
+    const int forced = env_conv_tile();
     // v_mfma_f32_16x16x32_bf16 by default: same cycles per FLOP as 32x32x16, but the chip holds a higher clock on it under load
     // (MI355X_MICROARCH.md, DVFS give-back item 7): 5-9 % less time on the 512 -> 1024 and 1024 -> 1024 layers, forward and dgrad
     // (profiles/r04_convgemm_microbench_v4.log); VMASR_CONV_MFMA=32 selects the 32x32x16 form
-    static const int mf = [] { const char *e = getenv("VMASR_CONV_MFMA"); return e ? atoi(e) : 16; }();
+    const int mf = env_conv_mfma();
     if (P.NB % 256 == 0 && forced != 128)
         return mf == 16 ? cg_launch_cfg<256, 256, 2, 4, 16>(P, epi, st, kid, bytes) : cg_launch_cfg<256, 256, 2, 4, 32>(P, epi, st, kid, bytes);
     // 256 x 128 (per wave 64 x 64): only for the 32-channel input side (K = 160: five K steps) — on the 128 -> 512 layer's dgrad it measured
@@ -876,8 +886,7 @@ VMASR_EXPORT int vmasr_conv_mfma_wgrad(const vmasr_cg_slot *slots, int32_t n, in
     VMASR_REQUIRE(vmasr_conv_mfma_supported(Cin, Cout, k, stride) && splits >= 1 && splits <= 64, VMASR_EINVAL,
                   "conv_mfma_wgrad: unsupported shape (Cin %d, Cout %d, k %d, stride %d, splits %d)", Cin, Cout, k, stride, splits);
     CwParams P = {};
-    static const int forced = [] { const char *e = getenv("VMASR_CONV_TILE"); return e ? atoi(e) : 0; }();
-    static const int mf = [] { const char *e = getenv("VMASR_CONV_MFMA"); return e ? atoi(e) : 16; }();
+    const int forced = env_conv_tile(), mf = env_conv_mfma();
     // 256 x 256 / 8 waves when both channel counts allow (with the 16x16x32 MFMA form: 597 -> 504-518 us on the 512 -> 1024 layer, 1 012 -> 945-960 us
     // on 1024 -> 1024, profiles/r04_convgemm_microbench_v5.log; with the 32x32x16 form it had measured no gain); VMASR_CONV_TILE=128 forces the small tile
     const bool big = Cout % 256 == 0 && Cin % 256 == 0 && forced != 128;

@@ -18,7 +18,6 @@ How it runs on the GPU (MIOpen has only `naive_conv_*` fallbacks for these (k,1)
   * `_ConvKx1Fn` (GEMMs on shifted views, no im2col) is an exact alternative kept opt-in
     (`VMASR_MPD_CONV=gemm`): measured slower than im2col + one GEMM.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -26,7 +25,7 @@ import torch.nn.functional as F
 from torch.nn.utils import parametrize
 from torch.nn.utils.parametrizations import weight_norm
 
-from . import _lib
+from . import _lib, knobs
 from .linear import _mm_acc, linear as _linear, weight_grad as _weight_grad
 
 __all__ = ["PeriodDiscriminator", "MultiPeriodDiscriminator", "spectral_norm", "plain_torch_ops"]
@@ -376,14 +375,24 @@ class _ConvKx1Fn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+def _kx1_mode():
+    """VMASR_MPD_CONV as conv_kx1 reads it: gemm | s3 (stride-3 layers only) | unfold (default: measured fastest; mfma means the same here)"""
+    return knobs.get("VMASR_MPD_CONV") or "unfold"
+
+
+def _batched_conv_mode():
+    """VMASR_MPD_CONV as the batched path reads it: mfma (default) = the implicit-GEMM kernels; any other value = not those"""
+    return knobs.get("VMASR_MPD_CONV") or "mfma"
+
+
 def conv_kx1(x, weight, bias, stride, pad):
     """(k,1) convolution of channel-last x (B, P, T, Cin) -> (B, P, T_out, Cout): the im2col-free GEMM form
     for the discriminator's two shapes (k 5 / stride 3, and stride 1), unfold + GEMM otherwise."""
     k = weight.shape[2]
-    mode = os.environ.get("VMASR_MPD_CONV", "unfold")    # gemm | s3 (stride-3 layers only) | unfold (default: measured fastest)
+    mode = _kx1_mode()
     ok = (stride == 3 and k == 5 and mode in ("gemm", "s3")) or (stride == 1 and mode == "gemm")
     if x.is_cuda and ok and x.shape[2] + 2 * pad >= k:
-        cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+        cdt = _lib.autocast_dtype(x)
         return _ConvKx1Fn.apply(x, weight, bias, stride, pad, cdt)
     return _conv_kx1_cl(x, weight, bias, stride, pad)
 
@@ -617,8 +626,8 @@ def _split_mode(K, N, cdt):
     """Which GEMMs of the fp32 discriminator run as error-compensated bf16 triples: the compute-bound ones
     (K*N >= 2^18: the 128->512, 512->1024 and 1024->1024 convolutions, 98 % of the FLOPs); the two small-K layers
     are memory-bound and stay plain fp32 GEMMs.  VMASR_MPD_GEMM=fp32 switches the triples off."""
-    return (cdt == torch.float32 and K * N >= int(os.environ.get("VMASR_MPD_SPLIT_MIN", str(1 << 18)))
-            and os.environ.get("VMASR_MPD_GEMM", "bf16x3") == "bf16x3")
+    return (cdt == torch.float32 and K * N >= knobs.get("VMASR_MPD_SPLIT_MIN")
+            and knobs.get("VMASR_MPD_GEMM") == "bf16x3")
 
 
 class _BatchedLinearSplitFn(torch.autograd.Function):
@@ -683,7 +692,7 @@ class _StackedConvSplitFn(torch.autograd.Function):
         w = weight.detach().float().contiguous()
         N = w.shape[1]
         fused = act and N % 4 == 0 and N <= 1024
-        kcat = fused and os.environ.get("VMASR_MPD_KCAT", "0") == "1"
+        kcat = fused and knobs.get("VMASR_MPD_KCAT")
         with torch.cuda.device(dev):
             if kcat:
                 # (opt-in, VMASR_MPD_KCAT=1 — measured SLOWER in round 3: 38.8 vs 38.0 ms per step.  The epilogue gains 0.36 ms
@@ -847,7 +856,7 @@ class _StackedConvMfmaFn(torch.autograd.Function):
         The bias gradient's column sums and the feature-matching term of the map between the two layers are part of the epilogue."""
         from . import convgemm as cg
         b = ctx.below
-        if b is None or "pre" not in b or os.environ.get("VMASR_MPD_FUSE_GELU_BWD", "1") != "1" or det_mode():
+        if b is None or "pre" not in b or not knobs.get("VMASR_MPD_FUSE_GELU_BWD") or _lib.det_mode():
             return False
         want_db = b["b_req"] and not skip_w
         want_f32 = b["C"] < 128 and b["x_req"]
@@ -958,13 +967,7 @@ def _poison(device):
 
 def _l1_mode():
     """how the 32 -> 128 layer runs: "f32" (default) exact-f32 MFMA implicit GEMM, "1" bf16x3 pairs (forward below the accuracy gate), "0" library GEMMs"""
-    return os.environ.get("VMASR_MPD_CONV_L1", "f32")
-
-
-def det_mode():
-    """deterministic-reduction mode of the library (VMASR_DETERMINISTIC=1 / vmasr_set_deterministic): the fused epilogue's bias-gradient
-    atomics have no ordered form, so the unfused chain (gelu_bwd_split with its tickets) runs there"""
-    return os.environ.get("VMASR_DETERMINISTIC", "0") == "1" or bool(_lib.lib().vmasr_get_deterministic())
+    return knobs.get("VMASR_MPD_CONV_L1")
 
 
 class _StackedConvFirstFn(torch.autograd.Function):
@@ -1198,7 +1201,7 @@ def _masked_l1_ok(yr, yg):
     return (yg.is_cuda and yr.is_cuda and yg.dtype == torch.float32 and yr.dtype == torch.float32 and yg.is_contiguous()
             and yr.is_contiguous() and not yr.requires_grad and yg.shape[0] <= 8 and yg.shape[0] == yr.shape[0]
             and (yg.shape[1] * yg.shape[2]) % 4 == 0 and (yr.shape[1] * yr.shape[2]) % 4 == 0
-            and os.environ.get("VMASR_FEAT_L1", "1") == "1")
+            and knobs.get("VMASR_FEAT_L1"))
 
 
 def feature_loss_stacked(real, gen):
@@ -1304,7 +1307,7 @@ class MultiPeriodDiscriminator(nn.Module):
         (channel-last (B, p, T', C) views) as running the PeriodDiscriminators one by one."""
         discs = list(self.discriminators)
         n, (B, _, T) = len(discs), x.shape
-        cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+        cdt = _lib.autocast_dtype(x)
         cur = []
         for d in discs:
             xp, p = x, d.period
@@ -1320,7 +1323,7 @@ class MultiPeriodDiscriminator(nn.Module):
             H1 = [(c.shape[2] + 2 * pad - k) // stride + 1 for c in cur]
             Ms = [B * p * h for p, h in zip(P, H1)]
             W = None
-            if os.environ.get("VMASR_SN_STACK", "1") == "1":
+            if knobs.get("VMASR_SN_STACK"):
                 # normalisation, stack and (tap, c) permutation of the layer's n weights in one launch; while the trainer
                 # holds the weights fixed for the step (frozen_weights()) the passes share it — one gradient path back
                 key = (li, bool(detach_weights))
@@ -1345,19 +1348,19 @@ class MultiPeriodDiscriminator(nn.Module):
             sgeom, src = None, cur
             pair, next_pair = next_pair, None     # the bf16 (hi, lo) pair of stacks[-1], if the previous layer's epilogue wrote it
             prev_link, this_link = this_link, None   # set by an MFMA layer: the layer above may finish its activation backward
-            if stacks and stacks[-1].dtype == cdt and os.environ.get("VMASR_STACK_INPUT", "1") == "1":
+            if stacks and stacks[-1].dtype == cdt and knobs.get("VMASR_STACK_INPUT"):
                 sgeom, src = tuple((B * p, c.shape[2]) for c, p in zip(cur, P)), (stacks[-1],)
             if (not act and stacks and cdt == torch.float32 and k == 3 and stride == 1 and pad == 1 and W.shape[1] == 1
-                    and stacks[-1].dtype == torch.float32 and os.environ.get("VMASR_CONV_POST", "1") == "1"
+                    and stacks[-1].dtype == torch.float32 and knobs.get("VMASR_CONV_POST")
                     and _lib.lib().vmasr_conv_post_supported(stacks[-1].shape[2], k)):
                 # the 1-channel output convolution straight on the previous layer's stacked maps (no column operand)
                 y = _StackedConvPostFn.apply(tuple(valid[-1]), tuple(c.shape[2] for c in cur), W, bstack, stacks[-1])
             elif (act and li == 0 and cdt == torch.float32 and k == 5 and stride == 3 and pad == 2 and W.shape[1] == 32 and W.shape[2] == 5
-                  and all(c.shape[3] == 1 for c in cur) and os.environ.get("VMASR_CONV_FIRST", "1") == "1"):
+                  and all(c.shape[3] == 1 for c in cur) and knobs.get("VMASR_CONV_FIRST")):
                 # the 1 -> 32 channel input convolution + GELU straight from the folded signals (no 5-column operand / K = 5 GEMM)
                 y = _StackedConvFirstFn.apply(_round_up(max(Ms), 256), W, bstack, *cur)
-            elif (cdt == torch.float32 and os.environ.get("VMASR_MPD_GEMM", "bf16x3") == "bf16x3" and act and sgeom is not None
-                  and os.environ.get("VMASR_MPD_CONV", "mfma") == "mfma"
+            elif (cdt == torch.float32 and knobs.get("VMASR_MPD_GEMM") == "bf16x3" and act and sgeom is not None
+                  and _batched_conv_mode() == "mfma"
                   and (cur[0].shape[3] >= 128 or _l1_mode() != "0")
                   # (shape, slot count and row count of the whole stacked launch: an MPD with more periods or a longer segment than
                   #  the launchers address falls through to the split-GEMM path below)
@@ -1386,7 +1389,7 @@ class MultiPeriodDiscriminator(nn.Module):
                 y = _BatchedLinearFn.apply(cols, W, bstack, cdt, act)
             tap = None
             if (act and y.requires_grad and y.dtype == torch.float32 and x.requires_grad
-                    and os.environ.get("VMASR_FEAT_TAP", "1") == "1"):
+                    and knobs.get("VMASR_FEAT_TAP")):
                 # generator phase: the map's gradient (next layer's + feature-matching loss's) is formed in one pass (_FeatTapFn)
                 holder = {}
                 y, token = _FeatTapFn.apply(y, holder)
@@ -1403,7 +1406,7 @@ class MultiPeriodDiscriminator(nn.Module):
         return [torch.flatten(c, 1, -1) for c in cur], StackedFeatures(fmaps, stacks, valid, taps)
 
     def _use_batched(self, x):
-        return (x.is_cuda and not _PLAIN_OPS[0] and os.environ.get("VMASR_MPD_BATCHED", "1") == "1"
+        return (x.is_cuda and not _PLAIN_OPS[0] and knobs.get("VMASR_MPD_BATCHED")
                 and len(self.discriminators) > 1)
 
     def forward_single(self, x, detach_weights=False):

@@ -5,25 +5,20 @@
 
 Compute: vm_asr_amd/csrc/dwconv.hip.  No CPU fallback.
 """
-import ctypes
 
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 __all__ = ["dwconv3x3_silu", "DWConv3x3SiLU"]
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 class DWConv3x3SiLU(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, x, weight, bias):
-        if not x.is_cuda:
-            raise RuntimeError("dwconv3x3_silu: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+        _lib.require_cuda("dwconv3x3_silu", x)
         B, C, H, W = x.shape
         if tuple(weight.shape) != (C, 1, 3, 3):
             raise RuntimeError("dwconv3x3_silu: weight must be (C,1,3,3)")

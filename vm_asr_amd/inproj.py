@@ -8,28 +8,21 @@ under bf16 autocast, for the fp32 / bf16 residual stream x (B, H, W, d), d in {8
 multiple of 32; `norm` a LayerNorm or nn.Identity.  One launch instead of LayerNorm + GEMM + ss2d_pre; backward = one kernel
 (recompute) + LayerNorm's backward + one weight-gradient GEMM.  No CPU fallback.
 """
-import ctypes
-import os
-
 import torch
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import ptr as _p
 from . import layernorm as _ln
 from .wgrad import weight_grad_finished
-from .linear import LP_ATTR, weight_grad
-from .mlp import _bf16_t
+from .linear import bf16_shadow, bf16_shadow_t
 
 __all__ = ["fused_in_proj", "supported"]
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def supported(x, norm, in_proj):
-    if os.environ.get("VMASR_FUSED_INPROJ", "1") != "1" or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
+    if not knobs.get("VMASR_FUSED_INPROJ") or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
         return False
-    if not (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+    if not _lib.bf16_autocast():
         return False
     if not isinstance(in_proj, torch.nn.Linear) or type(in_proj).__name__ == "Linear2d" or in_proj.bias is not None:
         return False
@@ -44,22 +37,15 @@ def supported(x, norm, in_proj):
     return bool(_lib.lib().vmasr_inproj_supported(int(d), int(in_proj.out_features), int(x.shape[1] * x.shape[2])))
 
 
-def _bf16(w):
-    sh = getattr(w, LP_ATTR, None)
-    return sh if (sh is not None and sh.dtype == torch.bfloat16) else w.detach().to(torch.bfloat16)
-
-
 class _InProjFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, weight, eps):
         B, H, W, d = x.shape
         L = H * W
-        x2 = x.reshape(-1, d)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _lib.rows2d(x, d)
         g32 = None if gamma is None else gamma.detach().float().contiguous()
         b32 = None if beta is None else beta.detach().float().contiguous()
-        wb = _bf16(weight).contiguous()
+        wb = bf16_shadow(weight).contiguous()
         with torch.cuda.device(x.device):
             xT = torch.empty((B, 2 * d, H, W), dtype=torch.bfloat16, device=x.device)
             sz = torch.empty((B, H, W, 2 * d), dtype=torch.bfloat16, device=x.device)
@@ -68,7 +54,7 @@ class _InProjFn(torch.autograd.Function):
         ctx.save_for_backward(x2, g32 if g32 is not None else torch.empty(0, device=x.device),
                               b32 if b32 is not None else torch.empty(0, device=x.device), wb)
         ctx.meta = (x.shape, eps, gamma is not None, None if gamma is None else gamma.dtype, None if beta is None else beta.dtype, weight.dtype)
-        ctx.wt = _bf16_t(weight, wb)
+        ctx.wt = bf16_shadow_t(weight, wb)
         if gamma is not None and any(ctx.needs_input_grad[1:3]):
             _ln.note_use(gamma, beta)
         ctx.fresh = lambda: gamma is not None and gamma.grad is None and beta.grad is None and _ln.used_once(gamma, beta)
@@ -76,7 +62,6 @@ class _InProjFn(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             _ln.note_use(weight)
         ctx.wparam = weight
-        ctx.fresh_w = lambda: weight.grad is None and weight.dtype == torch.float32 and _ln.used_once(weight)
         return xT, sz
 
     @staticmethod
@@ -114,12 +99,11 @@ class _InProjFn(torch.autograd.Function):
             else:
                 dx = dxn.to(x2.dtype)
         # (4d, d) fp32, split over the rows when few tiles; finished together with the pass' other weight gradients (wgrad.py)
-        dw, _ = weight_grad_finished(gpre, xn, d, ctx.wparam, None, ctx.fresh_w())
+        dw, _ = weight_grad_finished(gpre, xn, d, ctx.wparam, None, _ln.fresh(ctx.wparam))
         return dx.view(shape), dg, db, dw.to(wdt), None
 
 
 def fused_in_proj(x, norm, in_proj):
-    if not x.is_cuda:
-        raise RuntimeError("fused_in_proj: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("fused_in_proj", x)
     ln = isinstance(norm, torch.nn.LayerNorm)
     return _InProjFn.apply(x, norm.weight if ln else None, norm.bias if ln else None, in_proj.weight, norm.eps if ln else 0.0)

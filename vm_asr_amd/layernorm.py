@@ -7,19 +7,14 @@ every LayerNorm on the VM-ASR path (model/vmamba.py:767-769,1793,1817; model/mod
 F.layer_norm; the input is consumed in its own dtype (no separate cast pass).
 Tensors that are not on the GPU (host-side tests, the cpu_baseline leg) use F.layer_norm.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from ._lib import ptr as _p
 
 __all__ = ["LayerNorm", "layer_norm"]
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 # ---- deferred dgamma / dbeta -----------------------------------------------------------------------------------------
@@ -45,6 +40,12 @@ def note_use(*params):
 
 def used_once(*params):
     return all(_uses.get(id(t), 0) == 1 for t in params if t is not None)
+
+
+def fresh(*params):
+    """fp32 parameters without a .grad yet, each used once in this graph: autograd adopts the returned gradient tensor as their
+    .grad, so it may be filled at the end of the pass.  Ask in backward: .grad and the use counts are those of that moment."""
+    return all(p.grad is None and p.dtype == torch.float32 for p in params) and used_once(*params)
 
 
 _cb_queued = [False]   # the end-of-pass callback of the running backward has been queued
@@ -143,9 +144,7 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, out_dtype):
         C = x.shape[-1]
-        x2 = x.reshape(-1, C)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _lib.rows2d(x, C)
         rows = x2.shape[0]
         w32 = None if weight is None else weight.detach().float().contiguous()
         b32 = None if bias is None else bias.detach().float().contiguous()

@@ -9,31 +9,23 @@
   output tile reduced over all rows on one or two CUs (measured 170-380 us each, 12 ms/step);
 * everything else stays F.linear.
 """
-import ctypes
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import ptr as _p
 
 __all__ = ["Linear", "linear"]
 
 _MIN_ROWS = 16384
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 class _SmallLinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, out_dtype):
         out_f, in_f = weight.shape
-        x2 = x.reshape(-1, in_f)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _lib.rows2d(x, in_f)
         rows = x2.shape[0]
         w32 = weight.detach().float().contiguous()
         b32 = None if bias is None else bias.detach().float().contiguous()
@@ -71,7 +63,7 @@ class _SmallLinearFn(torch.autograd.Function):
         return (dx.view(shape) if need_dx else None, dw.to(wdt), db.to(bdt) if bdt is not None else None, None)
 
 
-_SPLITK_CHUNK = int(os.environ.get("VMASR_SPLITK_CHUNK", "2048"))   # fewest rows of one K-split
+_SPLITK_CHUNK = knobs.get("VMASR_SPLITK_CHUNK")   # fewest rows of one K-split
 
 
 def splitk_plan(rows, out_f, in_f):
@@ -129,6 +121,22 @@ LP_ATTR = "_vmasr_lp"   # parameter attribute: low-precision (autocast dtype) sh
 LPT_ATTR = "_vmasr_lpT"  # the same TRANSPOSED (2-D weights): operand of the fused kernels' backward (mlp.py, inproj.py, outproj.py)
 
 
+def bf16_shadow(w):
+    """The trainer's bf16 shadow of a parameter when it has one (no cast kernel), else a cast."""
+    sh = getattr(w, LP_ATTR, None)
+    return sh if (sh is not None and sh.dtype == torch.bfloat16) else w.detach().to(torch.bfloat16)
+
+
+def bf16_shadow_t(w, wb):
+    """W^T (bf16, contiguous) for the backward kernels when the trainer keeps a transposed shadow of parameter `w` and the
+    forward used its shadow `wb` (both are refreshed together by the AdamW kernel); None -> the caller transposes `wb` itself."""
+    sh = getattr(w, LPT_ATTR, None)
+    if (sh is not None and getattr(w, LP_ATTR, None) is wb and sh.dtype == torch.bfloat16 and wb.dim() == 2
+            and tuple(sh.shape) == (wb.shape[1], wb.shape[0])):
+        return sh
+    return None
+
+
 def _shadow(t, like, cdt):
     """The trainer's low-precision shadow of parameter `t` (viewed like `like`, a view of t), or None."""
     sh = getattr(t, LP_ATTR, None) if t is not None else None
@@ -141,7 +149,7 @@ def _skinny_ok(rows, in_f, out_f, x2, weight):
     """Many rows, few features: the streaming kernel of csrc/skinny.hip instead of a GEMM (VMASR_SKINNY=0: off)."""
     # where it beats the GEMM library under graph replay (tools/bench_skinny.py): >= 131 072 rows with <= 16 features each side (6.6-9.2 us
     # against 18.5-19.5 us); at 65 536 rows and 16-72 features hipBLASLt's 4-8 us are out of its reach (VMASR_SKINNY=all: every supported shape)
-    mode = os.environ.get("VMASR_SKINNY", "1")
+    mode = knobs.get("VMASR_SKINNY")
     if mode == "0" or not (x2.is_cuda and x2.dtype in (torch.float32, torch.bfloat16) and weight.dim() == 2):
         return False
     if mode != "all" and not (rows >= 131072 and in_f <= 16 and out_f <= 16):
@@ -252,7 +260,7 @@ def _use_f64acc(x, weight, bias):
     than hipBLASLt).  VMASR_LINEAR_F64ACC: "1" always, "0" never, default "auto" = only where no gradient is recorded (evaluation,
     the Tester, inference: the fp32 forward + LSD parity claim) — an amp=False TRAINING run keeps the library GEMMs.  The parity
     tests set "1" (tests/conftest.py) so that their fp32 backward is adjudicated at the same accuracy."""
-    mode = os.environ.get("VMASR_LINEAR_F64ACC", "auto")
+    mode = knobs.get("VMASR_LINEAR_F64ACC")
     if mode == "0" or (mode != "1" and torch.is_grad_enabled()):
         return False
     return (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32
@@ -267,7 +275,7 @@ def linear(x, weight, bias=None, shadow_of=None, bias_shadow_of=None):
     out_f, in_f = weight.shape
     if (x.is_cuda and x.dtype in (torch.float32, torch.float16, torch.bfloat16) and x.numel() // max(1, in_f) >= _MIN_ROWS
             and _lib.lib().vmasr_small_linear_supported(in_f, out_f)):
-        out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+        out_dtype = _lib.autocast_dtype(x)
         if out_dtype == x.dtype or x.dtype == torch.float32:
             return _SmallLinearFn.apply(x, weight, bias, out_dtype)
     if _use_f64acc(x, weight, bias):

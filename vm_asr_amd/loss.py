@@ -8,12 +8,12 @@ torch.stft — same arithmetic, and unlike rocFFT it can be captured in a HIP gr
 reference's window ("hann_window") is supported.
 """
 import ctypes
-import os
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import ptr as _p
 from . import stft as _stft
 
 __all__ = ["mae_loss", "mse_loss", "stft_magnitude", "STFTLoss", "MultiResolutionSTFTLoss", "HiFiGANLoss"]
@@ -35,10 +35,6 @@ def stft_magnitude(x, fft_size, hop_size, win_length, window, emphasize_high_fre
         # sic: the reference scales along dim 1 of the (B, frames, bins) tensor (model/loss.py:40-43)
         mag = mag * torch.linspace(1.0, 2.0, mag.size(1), device=x.device).view(1, -1, 1)
     return mag
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 class _STFTLossFn(torch.autograd.Function):
@@ -84,7 +80,7 @@ class STFTLoss(torch.nn.Module):
     def forward(self, x, y):
         # (the reference moves its window buffer to x.device on every call — a host->device copy per
         # step; the HIP front-end builds the window in-kernel, so nothing is copied here)
-        if x.is_cuda and y.is_cuda and not self.emphasize_high_freq and os.environ.get("VMASR_STFT_LOSS", "1") == "1":
+        if x.is_cuda and y.is_cuda and not self.emphasize_high_freq and knobs.get("VMASR_STFT_LOSS"):
             # both magnitudes, the three sums of the two loss terms and their gradient as three launches (csrc/stftloss.hip)
             rx, ix = _stft.stft_reim(x.float(), self.fft_size, self.shift_size, self.win_length)
             with torch.no_grad():
@@ -152,7 +148,7 @@ def _lsgan_terms(pairs):
     """sum over (tensor, target) pairs of mean((tensor - target)^2); one HIP launch when every tensor is fp32 on the GPU."""
     ts = [t for t, _ in pairs]
     if (ts and len(ts) <= 16 and all(t.is_cuda and t.dtype == torch.float32 and t.numel() > 0 for t in ts)
-            and os.environ.get("VMASR_LSGAN", "1") == "1"):
+            and knobs.get("VMASR_LSGAN")):
         return _LSGANFn.apply(tuple(float(c) for _, c in pairs), *ts)
     loss = 0
     for t, c in pairs:

@@ -9,29 +9,23 @@ MFMA 32x32x16, fp32 accumulation; the hidden activations never leave the registe
 recomputes the forward and produces dxn plus the bf16 operands of the weight-gradient GEMMs, then LayerNorm's backward
 (with the residual gradient folded in) and two GEMMs whose ones-column carries the bias gradients.  No CPU fallback.
 """
-import ctypes
-import os
-
 import torch
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import ptr as _p
 from . import layernorm as _ln
 from .wgrad import weight_grad_finished
-from .linear import LP_ATTR, LPT_ATTR, weight_grad
+from .linear import bf16_shadow, bf16_shadow_t
 
 __all__ = ["fused_mlp_residual", "supported"]
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def supported(x, norm, mlp):
     """GPU, bf16 autocast, fp32 channel-last stream, plain Mlp (GELU exact, no dropout) of a supported width.
     (The channel-first subclasses Linear2d / LayerNorm2d act on axis 1: never the row kernel, whatever x.shape[-1] is.)"""
-    if os.environ.get("VMASR_FUSED_MLP", "1") != "1" or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
+    if not knobs.get("VMASR_FUSED_MLP") or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
         return False
-    if not (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+    if not _lib.bf16_autocast():
         return False
     fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
     if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear) and isinstance(norm, torch.nn.LayerNorm)
@@ -47,33 +41,15 @@ def supported(x, norm, mlp):
     return bool(_lib.lib().vmasr_mlp_supported(int(d), int(fc1.out_features)))
 
 
-def _bf16(w):
-    """The trainer's bf16 shadow of a parameter when it has one (no cast kernel), else a cast."""
-    sh = getattr(w, LP_ATTR, None)
-    return sh if (sh is not None and sh.dtype == torch.bfloat16) else w.detach().to(torch.bfloat16)
-
-
-def _bf16_t(w, wb):
-    """W^T (bf16, contiguous) for the backward kernels when the trainer keeps a transposed shadow of parameter `w` and the
-    forward used its shadow `wb` (both are refreshed together by the AdamW kernel); None -> the caller transposes `wb` itself."""
-    sh = getattr(w, LPT_ATTR, None)
-    if (sh is not None and getattr(w, LP_ATTR, None) is wb and sh.dtype == torch.bfloat16 and wb.dim() == 2
-            and tuple(sh.shape) == (wb.shape[1], wb.shape[0])):
-        return sh
-    return None
-
-
 class _FusedMlpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, w1, b1, w2, b2, scale, eps):
         d = x.shape[-1]
-        x2 = x.reshape(-1, d)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _lib.rows2d(x, d)
         rows = x2.shape[0]
         g32, be32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
         b1f, b2f = b1.detach().float().contiguous(), b2.detach().float().contiguous()
-        w1b, w2b = _bf16(w1).contiguous(), _bf16(w2).contiguous()
+        w1b, w2b = bf16_shadow(w1).contiguous(), bf16_shadow(w2).contiguous()
         rps = rows // scale.numel() if scale is not None else 0
         sc = None if scale is None else scale.detach().float().contiguous().view(-1)
         with torch.cuda.device(x.device):
@@ -81,7 +57,7 @@ class _FusedMlpFn(torch.autograd.Function):
             _lib.check(_lib.lib().vmasr_mlp_fwd(_p(x2), _p(g32), _p(be32), float(eps), _p(w1b), _p(b1f), _p(w2b), _p(b2f), _p(sc), rps,
                                                 _p(y), rows, d, _lib.torch_dtype_code(x2.dtype), _lib.current_stream(x.device)), "mlp_fwd")
         ctx.save_for_backward(x2, g32, be32, w1b, b1f, w2b, sc)
-        ctx.wts = (_bf16_t(w1, w1b), _bf16_t(w2, w2b))
+        ctx.wts = (bf16_shadow_t(w1, w1b), bf16_shadow_t(w2, w2b))
         ctx.meta = (x.shape, eps, rps, gamma.dtype, beta.dtype, w1.dtype, b1.dtype, w2.dtype, b2.dtype)
         if any(ctx.needs_input_grad[1:3]):
             _ln.note_use(gamma, beta)
@@ -90,7 +66,6 @@ class _FusedMlpFn(torch.autograd.Function):
         if any(ctx.needs_input_grad[3:7]):
             _ln.note_use(w1, b1, w2, b2)
         ctx.wparams = (w1, b1, w2, b2)
-        ctx.fresh_w = lambda: (all(p.grad is None and p.dtype == torch.float32 for p in (w1, b1, w2, b2)) and _ln.used_once(w1, b1, w2, b2))
         return y.view(x.shape)
 
     @staticmethod
@@ -128,7 +103,7 @@ class _FusedMlpFn(torch.autograd.Function):
                        "layer_norm_bwd_res")
         # [dW1 | db1 | 0] = gpre^T xn_aug,  [dW2 | db2 | 0] = gys^T act_aug  (fp32 accumulation, split over the rows when few tiles);
         # the sum over the slabs and the split into contiguous dW / db: one launch for ALL queued GEMMs of the pass (wgrad.py)
-        fresh_w = ctx.fresh_w()
+        fresh_w = _ln.fresh(*ctx.wparams)
         dw1, db1 = weight_grad_finished(gpre, xn_aug, d, ctx.wparams[0], ctx.wparams[1], fresh_w)
         dw2, db2 = weight_grad_finished(gys, act_aug, hd, ctx.wparams[2], ctx.wparams[3], fresh_w)
         return (dx.view(shape), dg_.to(gdt), db_.to(bedt), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None)
@@ -136,6 +111,5 @@ class _FusedMlpFn(torch.autograd.Function):
 
 def fused_mlp_residual(x, norm, mlp, scale=None):
     """x + scale * mlp(norm(x)); `scale`: None or a (B,) / (B,1,1,1) per-sample tensor (DropPath keep mask / keep)."""
-    if not x.is_cuda:
-        raise RuntimeError("fused_mlp_residual: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("fused_mlp_residual", x)
     return _FusedMlpFn.apply(x, norm.weight, norm.bias, mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias, scale, norm.eps)

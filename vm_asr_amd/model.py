@@ -23,7 +23,6 @@ Reference behaviours that change numerics and are reproduced on purpose (SURVEY.
 Only the configuration family reachable from configs/*.yaml is built: 4-entry dims,
 norm "LN", patch-embed v2, down/upsample v1, output v3, interact dual/m2p/p2m/single.
 """
-import os
 from collections import OrderedDict
 from contextlib import nullcontext as _nullctx
 from copy import deepcopy
@@ -32,6 +31,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib, knobs
 from .stft import spectro2wav, wav2spectro
 from .layernorm import LayerNorm
 from .linear import Linear as _Linear, linear as _linear
@@ -97,8 +97,7 @@ class _Im2ColRowsFn(torch.autograd.Function):
 
 def _rows_ok(x):
     """dense input (every element of its storage addressed once: empty_strided in the backward is then a plain allocation)"""
-    import os
-    if os.environ.get("VMASR_IM2COL2D", "1") != "1" or x.dtype not in (torch.float32, torch.bfloat16):
+    if not knobs.get("VMASR_IM2COL2D") or x.dtype not in (torch.float32, torch.bfloat16):
         return False
     sz = sorted(zip(x.stride(), x.shape))
     exp = 1
@@ -125,7 +124,7 @@ class GemmConv2d(nn.Conv2d):
         Ho = (H + 2 * self.padding[0] - kh) // self.stride[0] + 1
         Wo = (W + 2 * self.padding[1] - kw) // self.stride[1] + 1
         if _rows_ok(x) and self.dilation == (1, 1) and self.groups == 1:
-            cdt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+            cdt = _lib.autocast_dtype(x)
             if cdt in (torch.float32, torch.bfloat16):
                 cols = _Im2ColRowsFn.apply(x, tuple(self.kernel_size), tuple(self.stride), tuple(self.padding), cdt)     # (B*Ho*Wo, C*kh*kw)
                 y = _linear(cols, self.weight.flatten(1), self.bias, shadow_of=self.weight)                             # (B*Ho*Wo, Cout)
@@ -321,8 +320,8 @@ class DualStreamInteractiveMambaUNet(MambaUNet):
         def phase(self, tag=None):       # context: the phase chain's stream
             if not self.on:
                 return _nullctx()
-            only = os.environ.get("VMASR_GEN_LANES")       # dev aid: which segments leave the main stream (pe,e0..e3,d0..d3,out,ia)
-            if only is not None and tag is not None and tag not in only.split(","):
+            only = knobs.get("VMASR_GEN_LANES")       # dev aid: which segments leave the main stream (pe,e0..e3,d0..d3,out,ia)
+            if only is not None and tag is not None and tag not in only:
                 return _OnMain(self)
             return torch.cuda.stream(self.side)
 
@@ -340,7 +339,7 @@ class DualStreamInteractiveMambaUNet(MambaUNet):
 
     def _lanes(self, x):
         side = None
-        mode = os.environ.get("VMASR_GEN_STREAMS", "auto")
+        mode = knobs.get("VMASR_GEN_STREAMS")
         # In captured steps only (the dependencies are then edges of the graph; "2eager" forces the eager path, a debugging aid), and
         # only with data-parallel library GEMMs (vm_asr_amd/hip_env.py: two concurrent stream-K GEMMs can stop the device).
         # "auto": where the trainer says so (self.phase_lane: generator-only steps, +14 ... +24 % clips/s at batch 35 ... 4) — beside

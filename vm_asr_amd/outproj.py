@@ -8,29 +8,22 @@ i.e. `out = self.out_proj(y)` (model/vmamba.py:1551; no bias, dropout p = 0) fol
 GEMM + (DropPath multiply +) add.  Backward: one kernel (dg = scale * gy . W in bf16 for ln_gate's backward, gys = scale * gy as
 the operand of the weight gradient) + one split-K GEMM; the stream's own gradient is gy itself.  No CPU fallback.
 """
-import ctypes
-import os
-
 import torch
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import ptr as _p
 from .wgrad import weight_grad_finished
 from . import layernorm as _ln
-from .linear import weight_grad
-from .mlp import _bf16, _bf16_t
+from .linear import bf16_shadow, bf16_shadow_t
 
 __all__ = ["fused_out_proj_residual", "supported"]
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def supported(g, out_proj, x, dropout=None):
     """GPU, bf16 autocast, bf16 gate output, fp32 / bf16 stream, bias-free out_proj of a supported width, no active dropout."""
-    if os.environ.get("VMASR_FUSED_OUTPROJ", "1") != "1" or not (g.is_cuda and x.is_cuda):
+    if not knobs.get("VMASR_FUSED_OUTPROJ") or not (g.is_cuda and x.is_cuda):
         return False
-    if not (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+    if not _lib.bf16_autocast():
         return False
     if g.dtype != torch.bfloat16 or x.dtype not in (torch.float32, torch.bfloat16):
         return False
@@ -48,13 +41,9 @@ class _OutProjFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, w, x, scale):
         d, di = x.shape[-1], g.shape[-1]
-        g2, x2 = g.reshape(-1, di), x.reshape(-1, d)
-        if not g2.is_contiguous():
-            g2 = g2.contiguous()
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        g2, x2 = _lib.rows2d(g, di), _lib.rows2d(x, d)
         rows = x2.shape[0]
-        wb = _bf16(w).contiguous()
+        wb = bf16_shadow(w).contiguous()
         rps = rows // scale.numel() if scale is not None else 0
         sc = None if scale is None else scale.detach().float().contiguous().view(-1)
         with torch.cuda.device(x.device):
@@ -62,12 +51,11 @@ class _OutProjFn(torch.autograd.Function):
             _lib.check(_lib.lib().vmasr_outproj_fwd(_p(g2), _p(wb), _p(x2), _p(sc), rps, _p(y), rows, d, _lib.torch_dtype_code(x2.dtype),
                                                     _lib.current_stream(x.device)), "outproj_fwd")
         ctx.save_for_backward(g2, wb, sc)
-        ctx.wt = _bf16_t(w, wb)
+        ctx.wt = bf16_shadow_t(w, wb)
         ctx.meta = (g.shape, x.shape, x2.dtype, rps, w.dtype)
         if ctx.needs_input_grad[1]:
             _ln.note_use(w)
         ctx.wparam = w
-        ctx.fresh_w = lambda: w.grad is None and w.dtype == torch.float32 and _ln.used_once(w)
         return y.view(x.shape)
 
     @staticmethod
@@ -90,12 +78,11 @@ class _OutProjFn(torch.autograd.Function):
                                                     _lib.current_stream(dev)), "outproj_bwd")
         dw = None
         if ctx.needs_input_grad[1]:                                          # (d, 2d) fp32; finished with the pass' other weight gradients
-            dw, _ = weight_grad_finished(gys, g2, di, ctx.wparam, None, ctx.fresh_w())
+            dw, _ = weight_grad_finished(gys, g2, di, ctx.wparam, None, _ln.fresh(ctx.wparam))
         return dg.view(gshape), None if dw is None else dw.to(wdt), gy.to(xdt) if ctx.needs_input_grad[2] else None, None
 
 
 def fused_out_proj_residual(g, out_proj, x, scale=None):
     """x + scale * out_proj(g); `scale`: None or a per-sample tensor (DropPath keep mask / keep)."""
-    if not x.is_cuda:
-        raise RuntimeError("fused_out_proj_residual: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("fused_out_proj_residual", x)
     return _OutProjFn.apply(g, out_proj.weight, x, scale)

@@ -16,6 +16,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import knobs
+
 __all__ = ["RcclComm", "CollectiveWatchdog", "available"]
 
 _DTYPES = {torch.float32: 7, torch.float16: 6, torch.bfloat16: 9, torch.float64: 8, torch.int32: 2, torch.int64: 4, torch.uint8: 1}
@@ -123,7 +125,7 @@ class CollectiveWatchdog:
     def __init__(self, timeout_s=None, poll_s=0.05, on_timeout=None):
         import queue
         import threading
-        self.timeout_s = float(os.environ.get("VMASR_RCCL_TIMEOUT_S", "300")) if timeout_s is None else float(timeout_s)
+        self.timeout_s = knobs.get("VMASR_RCCL_TIMEOUT_S") if timeout_s is None else float(timeout_s)
         self.poll_s = poll_s
         self.on_timeout = on_timeout or self._die
         self._q = queue.Queue()

@@ -17,6 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 __all__ = ["fwd", "bwd", "fwd_oflex", "bwd_oflex", "SelectiveScanCore", "SelectiveScanOflex", "selective_scan_fn", "tune"]
 
@@ -24,10 +25,6 @@ __all__ = ["fwd", "bwd", "fwd_oflex", "bwd_oflex", "SelectiveScanCore", "Selecti
 def _chk(cond, msg):
     if not cond:
         raise RuntimeError(msg)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _check_common(u, delta, A, B, C, D, delta_bias):

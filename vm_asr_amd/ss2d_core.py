@@ -8,27 +8,19 @@ high-resolution stages of every shipped config — with cross-scan, x_proj, dt_p
 fused around the scan (see the header of ss2d.hip).  Differentiable (one fused backward); no CPU fallback.
 """
 import ctypes
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import f32c as _f32c, ptr as _p
 
 __all__ = ["ss2d_core", "ss2d_core_pairs", "supported"]
 
 
 def supported(d_state, dt_rank, d_inner, H, W):
-    if os.environ.get("VMASR_SS2D_FUSED", "1") != "1":
+    if not knobs.get("VMASR_SS2D_FUSED"):
         return False
     return bool(_lib.lib().vmasr_ss2d_supported(int(d_state), int(dt_rank), int(d_inner), int(H), int(W)))
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _f32c(t, shape):
-    return t.detach().float().reshape(shape).contiguous()
 
 
 class _SS2DCoreFn(torch.autograd.Function):
@@ -91,13 +83,11 @@ class _SS2DCoreFn(torch.autograd.Function):
 
 
 def ss2d_core(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
-    if not x.is_cuda:
-        raise RuntimeError("ss2d_core: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("ss2d_core", x)
     return _SS2DCoreFn.apply(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, False)
 
 
 def ss2d_core_pairs(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
     """-> (out02 (B, D, H*W) in (h,w) order, out13 (B, D, W*H) in (w,h) order), both fp32: y = out02 + transpose(out13)."""
-    if not x.is_cuda:
-        raise RuntimeError("ss2d_core_pairs: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("ss2d_core_pairs", x)
     return _SS2DCoreFn.apply(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds, True)

@@ -7,11 +7,11 @@ which vm_asr_amd/ss2d_core.py (d_inner <= 32, dt_rank 1) does not take.  Forward
 GEMM (dW_x) and one sum (the per-wave parameter sums) — where the unfused chain ran 4 + 6 launches and their ATen glue.
 """
 import ctypes
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import f32c as _f32c, ptr as _p
 from . import layernorm as _ln
 from .linear import _mm_acc
 from .wgrad import finish_slabs
@@ -20,17 +20,9 @@ __all__ = ["ss2d_deep", "supported"]
 
 
 def supported(d_state, dt_rank, d_inner, H, W, dtype=torch.float32):
-    if os.environ.get("VMASR_SS2D_DEEP", "1") != "1" or dtype not in (torch.float32, torch.bfloat16):
+    if not knobs.get("VMASR_SS2D_DEEP") or dtype not in (torch.float32, torch.bfloat16):
         return False
     return bool(_lib.lib().vmasr_ss2d_deep_supported(int(d_state), int(dt_rank), int(d_inner), int(H), int(W)))
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _f32c(t, shape):
-    return t.detach().float().reshape(shape).contiguous()
 
 
 def _params(x, R, wx, wdt, b32, al, ds, xdbl):
@@ -104,6 +96,5 @@ class _SS2DDeepFn(torch.autograd.Function):
 
 def ss2d_deep(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds):
     """-> y (B, d_inner, H*W) fp32, the cross-merged output."""
-    if not x.is_cuda:
-        raise RuntimeError("ss2d_deep: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("ss2d_deep", x)
     return _SS2DDeepFn.apply(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)

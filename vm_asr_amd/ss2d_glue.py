@@ -6,23 +6,18 @@
         == out_norm(y.transpose(1,2).contiguous()).view(B,H,W,D).to(dtype) * z            model/vmamba.py:1528-1531,1550
 Both differentiable (one launch per direction); no CPU fallback.
 """
-import ctypes
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, knobs
+from ._lib import ptr as _p
 from . import layernorm as _ln
 
 __all__ = ["ss2d_pre", "ln_gate", "ln_gate_pairs", "pairs_supported", "supported"]
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def supported(D, L, dtype):
-    if os.environ.get("VMASR_SS2D_GLUE", "1") != "1" or dtype not in (torch.float32, torch.float16, torch.bfloat16):
+    if not knobs.get("VMASR_SS2D_GLUE") or dtype not in (torch.float32, torch.float16, torch.bfloat16):
         return False
     return bool(_lib.lib().vmasr_ss2d_glue_supported(int(D), int(L), _lib.torch_dtype_code(dtype)))
 
@@ -142,25 +137,22 @@ class _LNGatePairsFn(torch.autograd.Function):
 
 
 def pairs_supported(D, H, W, dtype):
-    if os.environ.get("VMASR_SS2D_PAIRS", "1") != "1" or dtype not in (torch.float32, torch.float16, torch.bfloat16):
+    if not knobs.get("VMASR_SS2D_PAIRS") or dtype not in (torch.float32, torch.float16, torch.bfloat16):
         return False
     return bool(_lib.lib().vmasr_ln_gate_pair_supported(int(D), int(H), int(W)))
 
 
 def ln_gate_pairs(y02, y13, sz, gamma, beta, eps):
     """== ln_gate(y02 + transpose_hw(y13), sz, gamma, beta, eps) without the merged tensor (sz: (B, H, W, D))."""
-    if not sz.is_cuda:
-        raise RuntimeError("ln_gate_pairs: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("ln_gate_pairs", sz)
     return _LNGatePairsFn.apply(y02, y13, sz, gamma, beta, eps)
 
 
 def ss2d_pre(xz):
-    if not xz.is_cuda:
-        raise RuntimeError("ss2d_pre: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("ss2d_pre", xz)
     return _PreFn.apply(xz)
 
 
 def ln_gate(y, sz, gamma, beta, eps):
-    if not sz.is_cuda:
-        raise RuntimeError("ln_gate: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("ln_gate", sz)
     return _LNGateFn.apply(y, sz, gamma, beta, eps)

@@ -11,23 +11,18 @@ wav2spectro is not differentiable (its input is the network input).
 
 Compute: vm_asr_amd/csrc/stft.hip.  No CPU fallback.
 """
-import ctypes
 from typing import Tuple
 
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 __all__ = ["wav2spectro", "spectro2wav", "stft_complex", "stft_reim", "ISTFTFunction", "STFTReImFunction"]
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _stft(waveform, n_fft, hop, win, normalized, logmag):
-    if not waveform.is_cuda:
-        raise RuntimeError("wav2spectro: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("wav2spectro", waveform)
     *other, length = waveform.shape
     w = waveform.reshape(-1, length).float().contiguous()
     Bn = w.shape[0]
@@ -62,8 +57,7 @@ class STFTReImFunction(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, wave, n_fft, hop, win, normalized):
-        if not wave.is_cuda:
-            raise RuntimeError("stft_reim: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+        _lib.require_cuda("stft_reim", wave)
         ctx.cfg = (wave.shape, n_fft, hop, win, bool(normalized))
         return _stft(wave, n_fft, hop, win, normalized, False)
 
@@ -125,8 +119,7 @@ def spectro2wav(mag: torch.Tensor, phase: torch.Tensor, n_fft: int, hop_length: 
                 spectro_scale: str) -> torch.Tensor:
     if spectro_scale != "log2":
         raise NotImplementedError("only spectro_scale='log2' is supported (reference dB branch needs torchaudio)")
-    if not mag.is_cuda:
-        raise RuntimeError("spectro2wav: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("spectro2wav", mag)
     *other, freqs, frames = mag.shape
     # the reference derives n_fft from the bin count (utils/stft.py:89)
     wav = ISTFTFunction.apply(mag.reshape(-1, freqs, frames), phase.reshape(-1, freqs, frames), hop_length,

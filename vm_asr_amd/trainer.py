@@ -34,6 +34,7 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
+from . import knobs
 from . import metric as metric_mod
 from .loss import HiFiGANLoss, MultiResolutionSTFTLoss, mae_loss, mse_loss
 
@@ -49,7 +50,7 @@ def init_distributed():
     if world > 1 and not dist.is_initialized():
         # "nccl" is RCCL on ROCm.  VMASR_DIST_BACKEND=gloo lets the multi-process path be exercised
         # on a machine with fewer GPUs than ranks (ranks then share devices; test use only).
-        backend = os.environ.get("VMASR_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
+        backend = knobs.get("VMASR_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
         kw = {}
         if torch.cuda.is_available():
             torch.cuda.set_device(local % torch.cuda.device_count())
@@ -58,7 +59,7 @@ def init_distributed():
                 # first collective, no "guessing device" warning, and graph capture never races a communicator bootstrap)
                 kw["device_id"] = torch.device("cuda", local % torch.cuda.device_count())
         import datetime
-        kw["timeout"] = datetime.timedelta(seconds=int(os.environ.get("VMASR_DIST_TIMEOUT_S", "600")))
+        kw["timeout"] = datetime.timedelta(seconds=knobs.get("VMASR_DIST_TIMEOUT_S"))
         dist.init_process_group(backend=backend, rank=rank, world_size=world, **kw)
     return rank, local, world
 
@@ -140,7 +141,7 @@ def build_optimizer(config, models, capturable=False):
         dev = next((p.device for g in groups for p in g["params"]), torch.device("cpu"))
         lr = torch.tensor(float(config.TRAIN.BASE_LR), device=dev) if capturable else config.TRAIN.BASE_LR
         # fused: one multi-tensor kernel per step instead of ~10 foreach passes over 44 M parameters
-        extra = dict(fused=True) if (capturable and on_gpu and os.environ.get("VMASR_FUSED_ADAMW", "1") == "1") \
+        extra = dict(fused=True) if (capturable and on_gpu and knobs.get("VMASR_FUSED_ADAMW")) \
             else dict(foreach=True if capturable else None)
         return torch.optim.AdamW(groups, lr=lr, eps=config.TRAIN.OPTIMIZER.EPS,
                                  betas=tuple(config.TRAIN.OPTIMIZER.BETAS), weight_decay=config.TRAIN.WEIGHT_DECAY,
@@ -412,7 +413,7 @@ class BaseTrainer:
             return
         msg = ("the checkpoint's config differs from the config this trainer was built from in fields the train step reads: "
                + "; ".join(diffs))
-        if os.environ.get("VMASR_RESUME_CONFIG_MISMATCH", "raise") != "warn":
+        if knobs.get("VMASR_RESUME_CONFIG_MISMATCH") != "warn":
             raise ValueError(msg + " (pass the matching --cfg / --opts, or set VMASR_RESUME_CONFIG_MISMATCH=warn to keep the built values)")
         self.logger.warning(msg + " — keeping the values the trainer was built from")
         stored.defrost()
@@ -630,7 +631,7 @@ class Trainer(BaseTrainer):
         SURVEY.md 8(e)), the generator's 9 MB as fp32 | "bf16": both.  The 16-bit wire is a NUMERICS CHANGE (3e-4 ... 9e-4 on the
         losses of one step) and is opt-in until a multi-GPU run has shown loss parity with the fp32 wire.  RCCL only: gloo is
         the CPU test backend."""
-        mode = os.environ.get("VMASR_GRAD_COMM", "fp32")
+        mode = knobs.get("VMASR_GRAD_COMM")
         if mode not in ("bf16", "mpd-bf16") or self.device.type != "cuda" or dist.get_backend() != "nccl":
             return torch.float32
         return torch.bfloat16 if (mode == "bf16" or key != "generator") else torch.float32
@@ -640,7 +641,7 @@ class Trainer(BaseTrainer):
         async_op: the call returns at once and the collective runs on RCCL's own stream, ordered after the CURRENT stream's work so
         far — the caller overlaps it with further work and joins it with _wait_reduces() before the optimiser reads the gradients.
         Capturable (RCCL): inside a stream capture the collective becomes a branch of the graph."""
-        emu = os.environ.get("VMASR_GRAD_COMM_EMULATE") if self.world == 1 else None
+        emu = knobs.get("VMASR_GRAD_COMM_EMULATE") if self.world == 1 else None
         if emu and key in self._flat and (emu == "bf16" or (emu == "mpd-bf16" and key != "generator")):
             # one rank, no wire: the 16-bit wire's ROUNDING applied to this rank's own gradient (tools/wire_dtype_run.py compares the
             # loss curves of 200 steps with and without it — the numerics question of the bf16 wire, answerable without a second GPU)
@@ -651,7 +652,7 @@ class Trainer(BaseTrainer):
             if key not in self._flat:
                 self._setup_flat(key, None)
             flat = self._flat[key]
-            if os.environ.get("VMASR_OVERLAP_REDUCE", "1") != "1":
+            if not knobs.get("VMASR_OVERLAP_REDUCE"):
                 async_op = False                    # escape hatch: collectives strictly between the graphs, no overlap
             avg = dist.get_backend() == "nccl"      # RCCL averages in the collective; gloo has no AVG
             buf = flat
@@ -662,7 +663,7 @@ class Trainer(BaseTrainer):
                 lp.copy_(flat)
                 buf = lp
             if getattr(self, "_direct_rccl", None) is not None and (torch.cuda.is_current_stream_capturing()
-                                                                     or os.environ.get("VMASR_RCCL_DIRECT", "0") == "1"):
+                                                                     or knobs.get("VMASR_RCCL_DIRECT")):
                 # RCCL's C API on a stream of its own, forked from the current one (vm_asr_amd/rccl.py: the process group's watchdog
                 # cannot live with captured collectives): a branch of the graph being captured
                 cs, cur = self._comm_stream(), torch.cuda.current_stream(self.device)
@@ -724,7 +725,7 @@ class Trainer(BaseTrainer):
         parameter gradient is read or accumulated in place before the pass ends — flat gradient buffers, no accumulation."""
         from . import layernorm
         layernorm.DEFER_REDUCE = (self.device.type == "cuda" and self.dp_mode == "flat" and self._gather
-                                  and os.environ.get("VMASR_LN_DEFER", "1") == "1")
+                                  and knobs.get("VMASR_LN_DEFER"))
         layernorm.reset_uses()
 
     def _two_streams(self):
@@ -732,7 +733,7 @@ class Trainer(BaseTrainer):
         the generator's ~1400 small launches on the main one.  Needs the shared fake pass (GPU, flat gradient buffers);
         off in deterministic mode (the ordered-accumulation tickets are per kernel, not per stream)."""
         from . import _lib, hip_env
-        mode = os.environ.get("VMASR_TWO_STREAM", "1")
+        mode = knobs.get("VMASR_TWO_STREAM")
         # ("force": test hook — the EAGER two-stream step in deterministic mode: generator and discriminator share no ticketed kernel id,
         #  so their ordered tails cannot meet; tests/test_determinism.py uses it to pin the stream layout's arithmetic bit for bit)
         if mode not in ("1", "force") or (_lib.det_mode() and mode != "force"):     # (the mode switched on by env var OR through the library)
@@ -780,15 +781,17 @@ class Trainer(BaseTrainer):
         lanes = (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
                  and bool(getattr(unwrap(self.models["generator"]), "phase_lane", False)))
         fwd_auto, bwd_auto = self.side_cu_limits(lanes)
-        cus = os.environ.get("VMASR_SIDE_CUS", str(bwd_auto))
-        if forward:
-            cus = os.environ.get("VMASR_SIDE_CUS_FWD", str(fwd_auto) if "VMASR_SIDE_CUS" not in os.environ else cus)
-        return convgemm.cu_limit(int(cus), 0 if forward else int(os.environ.get("VMASR_SIDE_CUS_MINC", "0")))
+        cus = knobs.get("VMASR_SIDE_CUS_FWD") if forward else None
+        if cus is None:
+            cus = knobs.get("VMASR_SIDE_CUS")
+        if cus is None:
+            cus = fwd_auto if forward else bwd_auto
+        return convgemm.cu_limit(cus, 0 if forward else knobs.get("VMASR_SIDE_CUS_MINC"))
 
     def _mark(self, name, stream=None):
         """VMASR_PHASE_EVENTS=1 (dev aid, tools/phase_probe.py): the device clock written to a buffer when `stream` reaches this point of the step
         (vmasr_mark_time: a one-thread kernel, so it is captured into the step's graph and a replay yields the step's real timeline)."""
-        if os.environ.get("VMASR_PHASE_EVENTS") != "1":
+        if not knobs.get("VMASR_PHASE_EVENTS"):
             return
         from . import _lib
         if not hasattr(self, "phase_marks"):
@@ -995,7 +998,7 @@ class Trainer(BaseTrainer):
             return False
         if self.config.TRAIN.ADVERSARIAL.GAN_LOSS_TYPE == "wgan-gp" or "mpd" not in self.config.TRAIN.ADVERSARIAL.DISCRIMINATORS:
             return False
-        return os.environ.get("VMASR_SHARE_FAKE_PASS", "1") == "1" and hasattr(unwrap(self.models["mpd"]), "_forward_batched")
+        return knobs.get("VMASR_SHARE_FAKE_PASS") and hasattr(unwrap(self.models["mpd"]), "_forward_batched")
 
     def _grad_targets(self, key):
         if key in self._flat_params:
@@ -1051,7 +1054,7 @@ class Trainer(BaseTrainer):
     def _hip_adamw_steps(self):
         """The HipAdamWStep objects of this trainer's optimisers, built once the optimiser states exist (after the first
         torch step) and the gradients live in the flat buffers; None -> use optimizer.step()."""
-        if self.device.type != "cuda" or self.dp_mode != "flat" or os.environ.get("VMASR_HIP_ADAMW", "1") != "1":
+        if self.device.type != "cuda" or self.dp_mode != "flat" or not knobs.get("VMASR_HIP_ADAMW"):
             return None
         cur = getattr(self, "_hip_adamw", None)
         if cur is not None and all(f.still_valid() for f in cur):
@@ -1088,7 +1091,7 @@ class Trainer(BaseTrainer):
         from .linear import LP_ATTR, LPT_ATTR
         self._shadow_src, self._shadow_dst, self._shadow_params = [], [], []
         self._shadow_t, self._shadow_t_view, self._shadow_t_src = {}, [], []      # transposed shadows of the 2-D weights
-        if not (self.amp and self.device.type == "cuda") or os.environ.get("VMASR_LP_SHADOWS", "1") != "1":
+        if not (self.amp and self.device.type == "cuda") or not knobs.get("VMASR_LP_SHADOWS"):
             return
         for key, m in self.models.items():
             if m is None:
@@ -1102,7 +1105,7 @@ class Trainer(BaseTrainer):
                     self._shadow_src.append(p.detach())
                     self._shadow_dst.append(lp)
                     self._shadow_params.append(p)
-                    if p.dim() == 2 and os.environ.get("VMASR_LP_SHADOWS_T", "1") == "1":
+                    if p.dim() == 2 and knobs.get("VMASR_LP_SHADOWS_T"):
                         lpt = lp.t().contiguous()          # refreshed with lp: by the AdamW kernel, or _refresh_shadows
                         setattr(p, LPT_ATTR, lpt)
                         self._shadow_t[id(p)] = lpt
@@ -1187,7 +1190,7 @@ class Trainer(BaseTrainer):
         # (profiles/r06_replay_segfault.md; a device synchronisation after the collection alone did not help: 2 of 12).  One
         # collection at the end, behind a device synchronisation.  VMASR_GRAPH_GC_GUARD=0: off.
         import gc as _gc
-        guard = _gc.isenabled() and os.environ.get("VMASR_GRAPH_GC_GUARD", "1") == "1"
+        guard = _gc.isenabled() and knobs.get("VMASR_GRAPH_GC_GUARD")
         if guard:
             _gc.collect()
             _gc.disable()
@@ -1216,7 +1219,7 @@ class Trainer(BaseTrainer):
         # fastest stays.
         from . import _lib, hip_env
         gen = unwrap(self.models["generator"])
-        mode = os.environ.get("VMASR_GEN_STREAMS", "auto")
+        mode = knobs.get("VMASR_GEN_STREAMS")
         self._step_batch = int(example_batch[0].shape[0])      # (not config.DATA.BATCH_SIZE: after a resume that is the checkpoint's)
         # never in deterministic mode: both branches launch the same ticketed kernels (sscan, xproj, dwconv, mlp, ss2d_glue) and the
         # ordered-accumulation tickets are per kernel id, ONE STREAM ONLY (csrc/common.h)
@@ -1238,15 +1241,6 @@ class Trainer(BaseTrainer):
             candidates = lane_variants
         else:
             candidates = [(False, None)] + lane_variants
-        # VMASR_STEP_VARIANT pins the layout (reproducible runs: the timed choice below rests on differences of 1-5 % and changes the
-        # order of the atomic additions): "one" | "lane" | "lane:<share of the CUs for the discriminator's backward>", e.g. lane:0.75
-        pin = os.environ.get("VMASR_STEP_VARIANT")
-        if pin and len(candidates) > 1:
-            want = (False, None) if pin == "one" else (True, float(pin.split(":", 1)[1]) if ":" in pin else None)
-            if want[0] and want[1] is None:
-                want = next((c for c in candidates if c[0]), want)
-            if want in candidates or (want[0] and lanes_possible):
-                candidates = [want]
 
         def use(variant):
             gen.phase_lane, self._lane_bwd_share = variant
@@ -1288,6 +1282,17 @@ class Trainer(BaseTrainer):
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)      # every rank takes the same decision: the slowest rank's time
             return float(t.item())
 
+        # VMASR_STEP_VARIANT pins the layout (reproducible runs: the timed choice below rests on differences of 1-5 % and changes the
+        # order of the atomic additions): "one" | "lane" | "lane:<share of the CUs for the discriminator's backward>", e.g. lane:0.75
+        want = knobs.get("VMASR_STEP_VARIANT")
+        if want is not None:
+            if want[0] and want[1] is None:
+                want = next((c for c in candidates if c[0]), want)
+            if len(candidates) > 1 and (want in candidates or (want[0] and lanes_possible)):
+                candidates = [want]
+            elif candidates != [want]:
+                self.logger.info(f"VMASR_STEP_VARIANT asks for {label(want)[:-3]}, which this configuration cannot run: "
+                                 f"choosing among {', '.join(label(c)[:-3] for c in candidates)}")
         use(candidates[0])
         ok = attempt()
         if (not ok and multi and dist.get_backend() == "nccl" and self.graph_collectives()):
@@ -1333,7 +1338,7 @@ class Trainer(BaseTrainer):
         Opt-in (VMASR_GRAPH_COLLECTIVES=1): that path has no process-group watchdog behind it and has not run with more than one
         real rank yet; the default keeps the collectives between the graphs on torch.distributed's communicator."""
         own = getattr(self, "_graph_collectives", None)
-        return os.environ.get("VMASR_GRAPH_COLLECTIVES", "0") == "1" if own is None else bool(own)
+        return knobs.get("VMASR_GRAPH_COLLECTIVES") if own is None else bool(own)
 
     @staticmethod
     def _pick_variant(variants, ms):

@@ -21,7 +21,6 @@ and LayerNorm stay in PyTorch (hipBLASLt / MIOpen).
 the product default is always the HIP operator set.
 """
 import math
-import os
 from functools import partial
 from typing import Any
 
@@ -30,6 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
+from . import knobs
 from .csm import CrossMergeHIP, CrossScanF32, CrossScanHIP
 from . import ss2d_core as _ss2d
 from . import ss2d_deep as _deep
@@ -171,7 +171,7 @@ def _strip(tag: str, value: str):
 # deep stages' weight gradients are (64 x 4) products over a 16384-long contraction that hipBLASLt runs on one CU per
 # direction (0.1 ms per call); the map's row-parallel kernels (d_inner >= 64) take 15-30 us per pass.  Train step of the
 # headline workload: einsums for d_inner >= 64: 45.2 ms; map up to 128: 41.8 ms; up to 256 (all it supports): 41.4 ms.
-_XPROJ_MAX_D = int(os.environ.get("VMASR_XPROJ_MAX_D", "512"))
+_XPROJ_MAX_D = knobs.get("VMASR_XPROJ_MAX_D")
 
 
 class SS2D(nn.Module):

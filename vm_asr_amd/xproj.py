@@ -6,17 +6,13 @@
 Equivalent to the two einsums + split + contiguous + float casts of SS2D.forward_corev2
 (model/vmamba.py:1473-1491), with fp32 accumulation.  No CPU fallback.
 """
-import ctypes
 
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 __all__ = ["x_proj_dt", "supported"]
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def supported(d_state, dt_rank, d_inner):
@@ -76,6 +72,5 @@ class _XProjFn(torch.autograd.Function):
 
 
 def x_proj_dt(xs, x_proj_weight, dt_projs_weight, d_state):
-    if not xs.is_cuda:
-        raise RuntimeError("x_proj_dt: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")
+    _lib.require_cuda("x_proj_dt", xs)
     return _XProjFn.apply(xs, x_proj_weight, dt_projs_weight, int(d_state))
