@@ -172,6 +172,18 @@ int vmasr_istft_bwd(const float *mag, const float *phase, const float *g, float 
                     float *dphase, int32_t B, int32_t F, int32_t M, int32_t hop, int32_t win,
                     vmasr_stream_t stream);
 
+/* SNR, LSD, LSD-HF, LSD-LF of a batch (model/metric.py:5-67) in two launches (csrc/metrics.hip): out, tgt (B,T) fp32 and
+ * hf (B) int64 on the device -> per_clip (B,4) fp32, columns snr, lsd, lsd_hf, lsd_lf.  STFT: center=True (reflect), periodic
+ * hann(n_fft), not normalised, F = n_fft/2+1 bins, M = 1+T/hop frames; per bin d = log10 max(|X|^2,1e-8) - log10 max(|Y|^2,1e-8);
+ * per frame sqrt(mean_f d^2) over all bins / bins [hf,F) / bins [0,hf) (each summed directly; an empty band gives NaN); per
+ * clip the mean over frames; snr = 20 log10(|tgt| / max(|out-tgt|, 1e-8)).  acc: NULL, or 5 doubles updated in place:
+ * acc[0..3] += the batch mean of each column (fp64, from the fp32 per-clip values in clip order), acc[4] += 1.  Fixed
+ * summation order, no atomics: bit-identical from call to call.  No host read.  n_fft a power of two in [64, 2048], hop > 0,
+ * 0 < B <= 65535, T > n_fft/2.  ws: scratch of vmasr_metrics_workspace() bytes. */
+size_t vmasr_metrics_workspace(int32_t B, int32_t T, int32_t n_fft, int32_t hop);
+int vmasr_metrics(const float *out, const float *tgt, const int64_t *hf, float *per_clip, double *acc, int32_t B, int32_t T,
+                  int32_t n_fft, int32_t hop, void *ws, size_t ws_bytes, vmasr_stream_t stream);
+
 /* Channel-last LayerNorm over the last dimension (F.layer_norm on (rows, C) with C <= 1024):
  * SS2D.out_norm, VSSBlock.norm/norm2, PatchMerging2D.norm, PatchExpanding.norm
  * (model/vmamba.py:767-769,1793,1817; model/model.py:70,105-108,620,631).
@@ -673,6 +685,7 @@ enum {
     VMASR_K_CONV_MFMA_WGRAD,    /* its weight gradient (transposed LDS reads)                                                                   */
     VMASR_K_WGRAD_FINISH,       /* sum over split-K slabs + bias column split-off of many weight gradients, one launch (csrc/wgrad.hip) */
     VMASR_K_SKINNY_LINEAR,      /* y = x W^T + b for >= 4096 rows and <= 96 features each side (csrc/skinny.hip) */
+    VMASR_K_METRICS,            /* SNR / LSD / LSD-HF / LSD-LF of a batch: packed out/tgt FFT per frame + finish (csrc/metrics.hip) */
     VMASR_K_COUNT
 };
 /* Deterministic-reduction switch (debug aid, off by default; the Python side turns it on for VMASR_DETERMINISTIC=1): the kernels whose

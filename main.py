@@ -42,6 +42,8 @@ def parse_option(argv=None):
     p.add_argument("--synthetic", type=int, default=64, help="number of synthetic VCTK-shaped clips per epoch")
     p.add_argument("--epochs", type=int, help="override TRAIN.EPOCHS")
     p.add_argument("--no-graphs", action="store_true", help="run the step eagerly instead of replaying HIP graphs")
+    p.add_argument("--step-metrics", action="store_true",
+                   help="metrics on every step / clip through the fused kernel (Trainer step_metrics, Tester fused_metrics)")
     args = p.parse_args(argv)
     from vm_asr_amd.config import get_config
     opts = list(args.opts or [])
@@ -78,7 +80,7 @@ def main(args, config):
         from vm_asr_amd.tester import Tester
         ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 10_000)
         loader = torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False)
-        res = Tester({"generator": models["generator"]}, metrics, config, device, loader, log).evaluate()
+        res = Tester({"generator": models["generator"]}, metrics, config, device, loader, log, fused_metrics=args.step_metrics).evaluate()
         print({k: round(v, 4) if isinstance(v, float) else v for k, v in res.items()})
         return
     ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 1000 * rank)
@@ -94,7 +96,8 @@ def main(args, config):
     steps = max(1, len(loader) // config.TRAIN.ACCUMULATION_STEPS)
     sched = {k: CosineWarmupScheduler(o, config.TRAIN.EPOCHS * steps, config.TRAIN.WARMUP_EPOCHS * steps, config.TRAIN.BASE_LR,
                                       config.TRAIN.MIN_LR, config.TRAIN.LR_SCHEDULER.WARMUP_PREFIX) for k, o in opts.items()}
-    tr = Trainer(models, metrics, opts, config, device, loader, None, sched, amp=config.AMP_ENABLE, gan=gan, logger=log)
+    tr = Trainer(models, metrics, opts, config, device, loader, None, sched, amp=config.AMP_ENABLE, gan=gan, logger=log,
+                 step_metrics=args.step_metrics)
     if graphs:
         first = next(iter(loader))
         tr.enable_graphs(tr._to_dev(first))

@@ -199,6 +199,8 @@ SYMBOLS = {
     "vmasr_istft_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_istft": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "vmasr_istft_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "vmasr_metrics_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "vmasr_metrics": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
 }
 
 _lib = None
@@ -292,7 +294,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 60
+K_COUNT = 61
 
 
 def zeros_f32(device, *shapes):

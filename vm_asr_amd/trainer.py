@@ -446,14 +446,25 @@ class _StreamWork:
 class Trainer(BaseTrainer):
     def __init__(self, models, metric_ftns, optimizers, config, device, data_loader_train, data_loader_val=None,
                  lr_schedulers=None, amp=False, gan=False, logger=None, len_epoch=None, dp_mode="flat",
-                 amp_scope="generator"):
+                 amp_scope="generator", step_metrics=False):
         """dp_mode: "flat" = gradients live in one flat buffer per model and are all-reduced with ONE
         RCCL call per optimiser per step (also what makes the step HIP-graph capturable);
         "ddp" = torch DistributedDataParallel buckets overlapped with backward.
         amp_scope: what autocast covers when `amp` is on.  "generator" = the reference's scope
         (trainer/trainer.py:138-139: only the generator forward; the losses and the discriminator run
-        outside autocast, i.e. in fp32); "step" = generator, losses and discriminator (bf16 MPD)."""
+        outside autocast, i.e. in fp32); "step" = generator, losses and discriminator (bf16 MPD).
+        step_metrics: evaluate the metrics on EVERY step (and every validation batch) and average them over the epoch, as the
+        reference does (trainer/trainer.py:158-182), through metric.Accumulator: one eager library call behind the step, no
+        host read until a line is printed / the epoch ends.  Off: the metrics are evaluated on the PRINT_FREQ steps only."""
         super().__init__(models, metric_ftns, optimizers, config, logger, resume_now=False)
+        self.step_metrics = bool(step_metrics)
+        if self.step_metrics:
+            known = {getattr(metric_mod, n): n for n in metric_mod.METRIC_ORDER}
+            for met in self.metric_ftns or []:
+                if met not in known:
+                    raise ValueError(f"step_metrics=True evaluates vm_asr_amd.metric's {metric_mod.METRIC_ORDER} only; "
+                                     f"got {getattr(met, '__name__', met)!r}")
+            self._metric_names = [known[met] for met in self.metric_ftns or []]
         self.dp_mode = dp_mode
         if amp_scope not in ("generator", "step"):
             raise ValueError(f"amp_scope='{amp_scope}'")
@@ -1356,11 +1367,17 @@ class Trainer(BaseTrainer):
             out[met.__name__] = float(met(wave_out.float().squeeze(1), wave_target.squeeze(1), hf=highcut))
         return out
 
+    def _accumulated(self, acc, reset):
+        """The running means of `acc` under the names of `metric_ftns` (one host read)."""
+        vals = acc.read(reset=reset)
+        return {k: vals[k] for k in self._metric_names if k in vals}
+
     def _train_epoch(self, epoch):
         for m in self.models.values():
             if m is not None:
                 m.train()
         sums, count, t0 = {}, 0, time.time()
+        acc = metric_mod.Accumulator(self.device) if self.step_metrics and self.metric_ftns else None
         self._micro = 0            # accumulation is keyed on the per-epoch batch index, as in the reference (trainer/trainer.py:146-156)
         last_idx = 0
         for batch_idx, batch in enumerate(self.data_loader):
@@ -1369,12 +1386,17 @@ class Trainer(BaseTrainer):
             last_idx = batch_idx   # index of the last PROCESSED batch (the loop variable is one past it after a `break`)
             wave_input, wave_target, highcut = self._to_dev(batch)
             wave_out, logs = self.train_step(wave_input, wave_target, highcut)
+            if acc is not None:
+                acc.update(wave_out, wave_target, highcut)     # eager, behind the step's graphs; no host read
             if batch_idx % self.config.PRINT_FREQ == 0 or batch_idx == self.len_epoch - 1:
                 vals = {k: float(v) for k, v in logs.items()}
-                vals.update(self._metrics(wave_out, wave_target, highcut))
+                if acc is None:
+                    vals.update(self._metrics(wave_out, wave_target, highcut))
                 for k, v in vals.items():
                     sums[k] = sums.get(k, 0.0) + v
                 count += 1
+                if acc is not None:
+                    vals.update(self._accumulated(acc, reset=False))    # shown: the running means over the steps so far
                 if self.rank == 0:
                     self.logger.info(f"Epoch {epoch} [{batch_idx + 1}/{self.len_epoch}] " +
                                      " ".join(f"{k}={v:.4f}" for k, v in vals.items()))
@@ -1388,6 +1410,8 @@ class Trainer(BaseTrainer):
             if self.gan and getattr(self, "lr_scheduler_D", None) is not None:
                 self.lr_scheduler_D.step_update(upd)
         self.epoch_log = {k: v / max(1, count) for k, v in sums.items()}
+        if acc is not None:
+            self.epoch_log.update(self._accumulated(acc, reset=True))    # means over ALL steps of the epoch
         self.epoch_log["epoch_seconds"] = time.time() - t0
 
     @torch.no_grad()
@@ -1396,15 +1420,23 @@ class Trainer(BaseTrainer):
             if m is not None:
                 m.eval()
         sums, count = {}, 0
+        acc = metric_mod.Accumulator(self.device) if self.step_metrics and self.metric_ftns else None
         for batch in self.data_loader_val:
             wave_input, wave_target, highcut = self._to_dev(batch)
             with torch.autocast(device_type=self.device.type, dtype=torch.bfloat16, enabled=self.amp):
                 wave_out = unwrap(self.models["generator"])(wave_input, highcut)
             vals = {"total_loss": float(sum(self._generator_losses(wave_out, wave_target).values()))} if not self.gan else {}
-            vals.update(self._metrics(wave_out, wave_target, highcut))
+            if acc is None:
+                vals.update(self._metrics(wave_out, wave_target, highcut))
+            else:
+                acc.update(wave_out, wave_target, highcut)
             for k, v in vals.items():
                 sums[k] = sums.get(k, 0.0) + v
             count += 1
+        if acc is not None and count:
+            # the sums of the batch means, read once; they join the cross-rank all-reduce below like the composed values do
+            per = dict(zip(metric_mod.METRIC_ORDER, acc.sums().tolist()))
+            sums.update({k: per[k] for k in self._metric_names})
         if self.world > 1:
             keys = sorted(sums)
             t = torch.tensor([sums[k] for k in keys] + [float(count)], device=self.device, dtype=torch.float64)
