@@ -56,7 +56,7 @@ int main(void){
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
         got = [int(v) for v in subprocess.check_output([exe]).split()]
     P, Q = _lib.SScanParams, _lib.SScanBwdParams
-    # vmasr_spectral_item is written from numpy (vm_asr_amd/discriminator.py:SpectralBatch): 5 pointers + 4 int32
+    # vmasr_spectral_item is written from numpy (vm_asr_amd/mpd_ops.py:SpectralBatch): 5 pointers + 4 int32
     want = [ctypes.sizeof(P), P.A_d_stride.offset, P.A_ptr.offset, P.x_ptr.offset, ctypes.sizeof(Q), Q.ws_bytes.offset,
             56, 40, 52]
     S, D = _lib.SS2DParams, _lib.SS2DDeepParams

@@ -808,3 +808,55 @@ def test_stacked_input_variants_equal_per_slot_inputs(split):
     assert torch.equal(res[0][1], res[1][1])
     for i, (p, H) in enumerate(geoms):
         assert not res[0][1][i, B * p * H:].any()
+
+
+# ---- which implementation each stacked layer takes (discriminator._layer_path) ------------------------------------
+# Recorded from the commit before _layer_path existed: its _forward_batched run once per setting with every stacked
+# Function.apply wrapped to log its class (profiles/mpd_bindings.md says how); rows = layers 0..4 and conv_post.
+_DEFAULT_PATHS = ("first", "mfma", "mfma", "mfma", "mfma", "post")
+_NOT_MFMA_PATHS = ("first", "gemm", "split", "split", "split", "post")
+_LAYER_PATHS = [
+    ({}, "f32", 5, _DEFAULT_PATHS),
+    ({"VMASR_MPD_CONV": "gemm"}, "f32", 5, _NOT_MFMA_PATHS),
+    ({"VMASR_MPD_CONV": "s3"}, "f32", 5, _NOT_MFMA_PATHS),
+    ({"VMASR_MPD_CONV": "unfold"}, "f32", 5, _NOT_MFMA_PATHS),
+    ({"VMASR_MPD_CONV_L1": "1"}, "f32", 5, _DEFAULT_PATHS),
+    ({"VMASR_MPD_CONV_L1": "0"}, "f32", 5, ("first", "gemm", "mfma", "mfma", "mfma", "post")),
+    ({"VMASR_MPD_GEMM": "fp32"}, "f32", 5, ("first", "gemm", "gemm", "gemm", "gemm", "post")),
+    ({"VMASR_CONV_POST": "0"}, "f32", 5, ("first", "mfma", "mfma", "mfma", "mfma", "gemm")),
+    ({"VMASR_CONV_FIRST": "0"}, "f32", 5, ("gemm", "mfma", "mfma", "mfma", "mfma", "post")),
+    ({"VMASR_STACK_INPUT": "0"}, "f32", 5, _NOT_MFMA_PATHS),
+    # (above every layer's K * N = 5120 * 1024 at most; with the implicit-GEMM kernels off, or the layers would not reach the split test)
+    ({"VMASR_MPD_CONV": "gemm", "VMASR_MPD_SPLIT_MIN": str(1 << 30)}, "f32", 5, ("first", "gemm", "gemm", "gemm", "gemm", "post")),
+    ({}, "bf16", 5, ("gemm",) * 6),
+    # seven periods: the launch query refuses the stride-3 layers' seven slots, which fall through; the stride-1 layer keeps the kernels
+    ({}, "f32", 7, ("first", "gemm", "split", "split", "mfma", "post")),
+]
+
+
+@pytest.mark.parametrize("env,cdt,n_periods,want", _LAYER_PATHS,
+                         ids=["-".join(f"{k[6:]}={v}" for k, v in e.items()) or f"default-{c}-{n}" for e, c, n, _ in _LAYER_PATHS])
+def test_layer_path_table(env, cdt, n_periods, want, monkeypatch):
+    """The path of each of the six stacked layers of the shipped MPD (hidden 32) at the vm_asr_48k_MPD workload's shapes — 2.555 s
+    segments at 48 kHz, yaml batch 4: the pass over [real; fake] sees 8 signals, the generator's pass 4 — under every path-selecting
+    switch.  No GPU: _layer_path takes numbers and dtypes, the two capability queries are host code."""
+    from vm_asr_amd import knobs
+    from vm_asr_amd.discriminator import _layer_path
+    for name in [name for name in os.environ if name.startswith("VMASR_") and name != "VMASR_LIB"]:
+        monkeypatch.delenv(name)
+    for name, v in env.items():
+        monkeypatch.setenv(name, v)
+    cdt = {"f32": torch.float32, "bf16": torch.bfloat16}[cdt]
+    periods, T, hidden = (2, 3, 5, 7, 11, 13, 17)[:n_periods], 122640, 32
+    chans = [1, hidden, hidden * 4, hidden * 16, hidden * 32, hidden * 32, 1]
+    for B in (4, 8):
+        H = [-(-T // p) for p in periods]                      # positions per sequence after the reflect padding to a multiple of p
+        got = []
+        for li in range(6):
+            k, stride, pad = ((5, 3, 2), (5, 3, 2), (5, 3, 2), (5, 3, 2), (5, 1, 2), (3, 1, 1))[li]
+            H1 = [(h + 2 * pad - k) // stride + 1 for h in H]
+            # every path hands the next layer a stacked output in the compute dtype, read as it is unless VMASR_STACK_INPUT=0
+            got.append(_layer_path(li, li < 5, cdt, cdt if li else None, li > 0 and knobs.get("VMASR_STACK_INPUT"), k, stride, pad, chans[li], chans[li + 1], len(periods),
+                                   max(B * p * h for p, h in zip(periods, H1)), max(B * p * h for p, h in zip(periods, H))))
+            H = H1
+        assert tuple(got) == want, (B, got)

@@ -25,7 +25,8 @@ import torch.nn.functional as F
 from torch.nn.utils import parametrize
 from torch.nn.utils.parametrizations import weight_norm
 
-from . import _lib, knobs
+from . import _lib, knobs, mpd_ops as bind
+from .mpd_ops import SpectralBatch, _slot_arrays, geom_of as _geom, split_bf16  # noqa: F401  (tests and tools import them from here)
 from .linear import _mm_acc, linear as _linear, weight_grad as _weight_grad
 
 __all__ = ["PeriodDiscriminator", "MultiPeriodDiscriminator", "spectral_norm", "plain_torch_ops"]
@@ -70,16 +71,7 @@ class _SpectralNorm(nn.Module):
     @torch.autograd.no_grad()
     def _power_method(self, w, n):
         if w.is_cuda and n > 0 and w.dtype == torch.float32:
-            import ctypes
-            from . import _lib
-            w = w.contiguous()
-            R, C = w.shape
-            ws = torch.empty(R + C, dtype=torch.float32, device=w.device)
-            p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-            with torch.cuda.device(w.device):
-                _lib.check(_lib.lib().vmasr_spectral_power_iter(p(w), p(self._u), p(self._v), p(ws), R, C, int(n),
-                                                                float(self.eps), _lib.current_stream(w.device)),
-                           "spectral_power_iter")
+            bind.spectral_power_iter(w.contiguous(), self._u, self._v, n, self.eps)
             return
         for _ in range(n):
             self._u = F.normalize((w @ self._v.unsqueeze(1)).squeeze(1), dim=0, eps=self.eps, out=self._u)
@@ -119,11 +111,6 @@ class _SNDivFn(torch.autograd.Function):
         return gw.view_as(out), None, None, None
 
 
-def _ptr_array(tensors):
-    import ctypes
-    return (ctypes.c_void_p * len(tensors))(*[ctypes.c_void_p(t.data_ptr()) for t in tensors])
-
-
 class _SNStackFn(torch.autograd.Function):
     """The spectrally normalised weights of one layer of all n period discriminators as ONE (n, N, k*Cin) GEMM operand in
     (tap, channel) column order: out[s] = permute(W_s / sigma_s) with sigma_s, u_s, v_s from the batched power iteration
@@ -133,29 +120,16 @@ class _SNStackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, n, *args):
         sig, us, vs, ws = args[:n], args[n:2 * n], args[2 * n:3 * n], args[3 * n:]
-        N, Cin, k = ws[0].shape[0], ws[0].shape[1], ws[0].shape[2]
-        dev = ws[0].device
-        wc = [w.detach().contiguous() for w in ws]
-        with torch.cuda.device(dev):
-            out = torch.empty((n, N, k * Cin), dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().vmasr_sn_stack_fwd(_ptr_array(wc), _ptr_array(sig), n, out.data_ptr(), N, Cin, k,
-                                                     _lib.current_stream(dev)), "sn_stack_fwd")
+        out = bind.sn_stack_fwd([w.detach().contiguous() for w in ws], sig)
         ctx.save_for_backward(out, *sig, *us, *vs)
-        ctx.geom = (n, N, Cin, k, [w.shape for w in ws])
+        ctx.geom = (n, [w.shape for w in ws])
         return out
 
     @staticmethod
     def backward(ctx, dW):
-        n, N, Cin, k, shapes = ctx.geom
+        n, shapes = ctx.geom
         out, *rest = ctx.saved_tensors
-        sig, us, vs = rest[:n], rest[n:2 * n], rest[2 * n:3 * n]
-        dW = dW.float().contiguous()
-        lib, dev = _lib.lib(), dW.device
-        with torch.cuda.device(dev):
-            gws = [torch.empty(shp, dtype=torch.float32, device=dev) for shp in shapes]
-            partials = torch.empty(n * lib.vmasr_sn_dot_blocks(), dtype=torch.float64, device=dev)
-            _lib.check(lib.vmasr_sn_stack_bwd(dW.data_ptr(), out.data_ptr(), _ptr_array(gws), _ptr_array(sig), _ptr_array(us), _ptr_array(vs),
-                                              n, partials.data_ptr(), N, Cin, k, _lib.current_stream(dev)), "sn_stack_bwd")
+        gws = bind.sn_stack_bwd(dW.float().contiguous(), out, rest[:n], rest[n:2 * n], rest[2 * n:3 * n], shapes)
         return (None, *([None] * (3 * n)), *gws)
 
 
@@ -179,59 +153,6 @@ def _sn_stack(layers):
     return _SNStackFn.apply(n, *[sn._sigma_pre for sn in sns], *[sn._u for sn in sns], *[sn._v for sn in sns], *origs)
 
 
-class SpectralBatch:
-    """Power iteration of MANY _SpectralNorm modules in one launch per phase
-    (vmasr_spectral_power_iter_batched): the descriptor table (pointers to the fp32 weights, u, v and
-    scratch) is built once on the device; the pointers are those of parameters and buffers, which live
-    at fixed addresses for the life of the model on its device."""
-
-    def __init__(self, modules, weights):
-        import numpy as np
-        assert 0 < len(modules) <= 64
-        dev = weights[0].device
-        self.modules, self.eps = list(modules), float(modules[0].eps)
-        mats = [w.detach() for w in weights]
-        assert all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() for w in mats)
-        shapes = [(w.shape[0], w[0].numel()) for w in mats]
-        self.ws = torch.zeros(sum(r + c for r, c in shapes), dtype=torch.float32, device=dev)
-        item = np.dtype([("W", "u8"), ("u", "u8"), ("v", "u8"), ("t", "u8"), ("s", "u8"),
-                         ("R", "i4"), ("C", "i4"), ("rb", "i4"), ("ct", "i4")])
-        tab = np.zeros(len(mats), dtype=item)
-        off = rb = ct = 0
-        for i, (m, w, (r, c)) in enumerate(zip(self.modules, mats, shapes)):
-            tab[i] = (w.data_ptr(), m._u.data_ptr(), m._v.data_ptr(), self.ws.data_ptr() + 4 * off,
-                      self.ws.data_ptr() + 4 * (off + r), r, c, rb, ct)
-            off += r + c
-            rb += -(-r // 4)
-            ct += -(-c // 1024) * -(-r // 32)
-        self.n, self.row_blocks, self.col_tiles = len(mats), rb, ct
-        self.weight_bytes = sum(4 * r * c for r, c in shapes)
-        self.ptrs = [(w.data_ptr(), m._u.data_ptr(), m._v.data_ptr()) for m, w in zip(self.modules, mats)]
-        self.sigma = torch.ones(len(mats), dtype=torch.float32, device=dev)
-        self.table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
-
-    def matches(self, weights):
-        return len(weights) == self.n and all(
-            (w.data_ptr(), m._u.data_ptr(), m._v.data_ptr()) == p for m, w, p in zip(self.modules, weights, self.ptrs))
-
-    @torch.no_grad()
-    def run(self, n_iter, with_sigma=False):
-        """n_iter power iterations of every matrix; with_sigma: also sigma_m = u^T W v, handed to the modules
-        (`_sigma_pre`, a view of self.sigma) until clear_sigma()."""
-        dev = self.table.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().vmasr_spectral_power_iter_batched(
-                self.table.data_ptr(), self.n, self.row_blocks, self.col_tiles, self.weight_bytes, int(n_iter), self.eps,
-                self.sigma.data_ptr() if with_sigma else None, _lib.current_stream(dev)), "spectral_power_iter_batched")
-        if with_sigma:
-            for i, m in enumerate(self.modules):
-                object.__setattr__(m, "_sigma_pre", self.sigma[i])
-
-    def clear_sigma(self):
-        for m in self.modules:
-            object.__setattr__(m, "_sigma_pre", None)
-
-
 def spectral_norm(module, name="weight", n_power_iterations=1, eps=1e-12):
     parametrize.register_parametrization(module, name, _SpectralNorm(getattr(module, name), n_power_iterations, eps))
     return module
@@ -244,24 +165,14 @@ class _Im2ColFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k, stride, pad):
         B, P, H, C = x.shape
-        xc = x.contiguous()
-        H1 = (H + 2 * pad - k) // stride + 1
-        with torch.cuda.device(x.device):
-            cols = torch.empty((B, P, H1, k * C), dtype=x.dtype, device=x.device)
-            _lib.check(_lib.lib().vmasr_im2col_kx1(xc.data_ptr(), cols.data_ptr(), B * P, H, C, k, stride, pad, 0,
-                                                   _lib.torch_dtype_code(x.dtype), _lib.current_stream(x.device)), "im2col_kx1")
-        ctx.geom = (B, P, H, C, k, stride, pad)
-        return cols
+        cols = bind.im2col_kx1([x.contiguous()], _geom([x]), C, k, stride, pad)
+        ctx.geom = (tuple(x.shape), k, stride, pad)
+        return cols.view(B, P, -1, k * C)
 
     @staticmethod
     def backward(ctx, g):
-        B, P, H, C, k, stride, pad = ctx.geom
-        g = g.contiguous()
-        with torch.cuda.device(g.device):
-            dx = torch.empty((B, P, H, C), dtype=g.dtype, device=g.device)
-            _lib.check(_lib.lib().vmasr_col2im_kx1(g.data_ptr(), dx.data_ptr(), B * P, H, C, k, stride, pad,
-                                                   _lib.torch_dtype_code(g.dtype), _lib.current_stream(g.device)), "col2im_kx1")
-        return dx, None, None, None
+        shape, k, stride, pad = ctx.geom
+        return bind.col2im_kx1(g.contiguous(), shape, k, stride, pad), None, None, None
 
 
 def _conv_kx1_cl(x, weight, bias, stride, pad):
@@ -407,16 +318,6 @@ def _round_up(v, m):
     return -(-v // m) * m
 
 
-def _slot_arrays(ptrs, Ns, Hs=None):
-    """ctypes host arrays (device pointers, per-slot sizes) of the multi-slot entry points (include/vmasr_hip.h)."""
-    import ctypes
-    n = len(ptrs)
-    a = (ctypes.c_void_p * n)(*[ctypes.c_void_p(p) if p else None for p in ptrs])
-    b = (ctypes.c_int64 * n)(*Ns)
-    c = (ctypes.c_int32 * n)(*Hs) if Hs is not None else None
-    return a, b, c
-
-
 class _StackedIm2ColFn(torch.autograd.Function):
     """n channel-last inputs (B, P_i, H_i, C) -> one (n, rows, k*C) column tensor, slot i holding the im2col
     of input i in its first B*P_i*H1_i rows and zeros below (vmasr_im2col_kx1 with rows_out).
@@ -426,43 +327,21 @@ class _StackedIm2ColFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, k, stride, pad, rows, geom, *xs):
-        lib = _lib.lib()
         if geom is not None:
-            x = xs[0].contiguous()
-            n, rows_in, C = x.shape
-            dt, dev, step = x.dtype, x.device, rows_in * C * x.element_size()
-            srcs = [(x.data_ptr() + i * step, N, H) for i, (N, H) in enumerate(geom)]
-            ctx.geom = (k, stride, pad, None, tuple(geom), (n, rows_in, C))
+            src = xs[0].contiguous()
+            ctx.geom = (k, stride, pad, None, tuple(geom), tuple(src.shape))
         else:
-            C, dt, dev = xs[0].shape[3], xs[0].dtype, xs[0].device
-            xcs = [x.contiguous() for x in xs]
-            srcs = [(x.data_ptr(), x.shape[0] * x.shape[1], x.shape[2]) for x in xcs]
+            src, geom = [x.contiguous() for x in xs], _geom(xs)
             ctx.geom = (k, stride, pad, [tuple(x.shape) for x in xs], None, None)
-        with torch.cuda.device(dev):
-            cols = torch.empty((len(srcs), rows, k * C), dtype=dt, device=dev)
-            for i, (ptr, N, H) in enumerate(srcs):
-                _lib.check(lib.vmasr_im2col_kx1(ptr, cols[i].data_ptr(), N, H, C, k, stride, pad, rows,
-                                                _lib.torch_dtype_code(dt), _lib.current_stream(dev)), "im2col_kx1")
-        return cols
+        return bind.im2col_kx1(src, geom, src[0].shape[-1], k, stride, pad, rows)
 
     @staticmethod
     def backward(ctx, g):
         k, stride, pad, shapes, geom, sshape = ctx.geom
         g = g.contiguous()
-        lib = _lib.lib()
-        with torch.cuda.device(g.device):
-            if geom is not None:
-                n, rows_in, C = sshape
-                dx = torch.empty(sshape, dtype=g.dtype, device=g.device)
-                _, Ns, Hs = _slot_arrays([0] * n, [N for N, _ in geom], [H for _, H in geom])
-                _lib.check(lib.vmasr_col2im_kx1_stacked(g.data_ptr(), dx.data_ptr(), Ns, Hs, n, C, k, stride, pad, g.shape[1], rows_in,
-                                                        _lib.torch_dtype_code(g.dtype), _lib.current_stream(g.device)), "col2im_kx1_stacked")
-                return (None, None, None, None, None, dx)
-            dxs = [torch.empty(shp, dtype=g.dtype, device=g.device) for shp in shapes]
-            ptrs, Ns, Hs = _slot_arrays([d.data_ptr() for d in dxs], [B * P for B, P, _, _ in shapes], [H for _, _, H, _ in shapes])
-            _lib.check(lib.vmasr_col2im_kx1_multi(g.data_ptr(), ptrs, Ns, Hs, len(shapes), shapes[0][3], k, stride, pad, g.shape[1],
-                                                  _lib.torch_dtype_code(g.dtype), _lib.current_stream(g.device)), "col2im_kx1_multi")
-        return (None, None, None, None, None, *dxs)
+        if geom is not None:
+            return (None, None, None, None, None, bind.col2im_kx1_stacked(g, geom, sshape, k, stride, pad))
+        return (None, None, None, None, None, *bind.col2im_kx1_multi(g, shapes, k, stride, pad))
 
 
 # Backward-phase switch of the trainer's shared fake pass: while the GENERATOR loss is back-propagated through
@@ -509,10 +388,7 @@ class _BatchedLinearFn(torch.autograd.Function):
         pre = None
         if fused:
             pre = y
-            with torch.cuda.device(y.device):
-                y = torch.empty_like(pre)
-                _lib.check(_lib.lib().vmasr_bias_gelu_fwd(pre.data_ptr(), bias.detach().float().contiguous().data_ptr(), y.data_ptr(),
-                                                          n, M, N, 1, _lib.current_stream(y.device)), "bias_gelu_fwd")
+            y = bind.bias_gelu_fwd(pre, bias.detach().float().contiguous())
         else:
             y.add_(bias.detach().to(cdt).unsqueeze(1))
             if act:
@@ -533,12 +409,7 @@ class _BatchedLinearFn(torch.autograd.Function):
         db = None
         if fused:
             want_db = ctx.needs_input_grad[2] and not skip_w
-            with torch.cuda.device(gy.device):
-                gx = torch.empty_like(gy)
-                db32, = _lib.zeros_f32(gy.device, (n, N) if want_db else None)
-                _lib.check(_lib.lib().vmasr_gelu_bwd(rest[0].data_ptr(), gy.data_ptr(), gx.data_ptr(), db32.data_ptr() if want_db else None,
-                                                     n, M, N, _lib.current_stream(gy.device)), "gelu_bwd")
-            gy = gx
+            gy, db32 = bind.gelu_bwd(rest[0], gy, want_db=want_db)
             db = db32.to(bdt) if want_db else None
         elif act:
             gy = torch.ops.aten.gelu_backward(gy, rest[0])
@@ -560,17 +431,6 @@ class _BatchedLinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[2] and not fused:
             db = gy.sum(1, dtype=torch.float32 if gy.dtype in (torch.float16, torch.bfloat16) else None).to(bdt)
         return dcols, dw, db, None, None
-
-
-def split_bf16(x):
-    """fp32 tensor -> (hi, lo) bf16 with x = hi + lo up to 2^-17 |x| (vm_asr_amd/csrc/split.hip)."""
-    x = x.contiguous()
-    with torch.cuda.device(x.device):
-        hi = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-        lo = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-        _lib.check(_lib.lib().vmasr_split_bf16(x.data_ptr(), hi.data_ptr(), lo.data_ptr(), x.numel(),
-                                               _lib.current_stream(x.device)), "split_bf16")
-    return hi, lo
 
 
 def _bmm3(ah, al, bh, bl):
@@ -615,10 +475,7 @@ def _dw3(gh, gl, ch, cl, wdt):
     torch.bmm(glt, v(ch), out_dtype=torch.float32, out=parts[1])
     torch.bmm(ght, v(cl), out_dtype=torch.float32, out=parts[2])
     if (N * K) % 4 == 0 and n <= 65535:
-        with torch.cuda.device(gh.device):
-            dw = torch.empty((n, N, K), dtype=torch.float32, device=gh.device)
-            _lib.check(_lib.lib().vmasr_sum_parts(parts.data_ptr(), dw.data_ptr(), 3, n, S, N * K, _lib.current_stream(gh.device)), "sum_parts")
-        return dw.to(wdt)
+        return bind.sum_parts(parts, 3, n, S, (N, K)).to(wdt)
     return parts.view(3, n, S, N, K).sum((0, 2)).to(wdt)
 
 
@@ -677,44 +534,31 @@ class _StackedConvSplitFn(torch.autograd.Function):
         and the bf16 split of the incoming gradient into one pass, csrc/split.hip).
         geom = ((N_i, H_i), ...): the inputs are the slots of ONE stacked fp32 tensor xs[0] (n, rows_in, C) — the previous
         layer's stacked output — and the backward returns its stacked gradient (see _StackedIm2ColFn)."""
-        lib = _lib.lib()
+        sgeom = tuple(geom) if geom is not None else None
         if geom is not None:
-            xs0 = xs[0].float().contiguous()
-            n, rows_in, C = xs0.shape
-            dev, K = xs0.device, k * C
-            xcs = [xs0]
-            ptrs, Ns, Hs = _slot_arrays([xs0.data_ptr() + i * rows_in * C * 4 for i in range(n)], [N for N, _ in geom], [H for _, H in geom])
+            src = xs[0].float().contiguous()
         else:
-            C, dev = xs[0].shape[3], xs[0].device
-            n, K = len(xs), k * C
-            xcs = [x.float().contiguous() for x in xs]
-            ptrs, Ns, Hs = _slot_arrays([x.data_ptr() for x in xcs], [x.shape[0] * x.shape[1] for x in xcs], [x.shape[2] for x in xcs])
+            src, geom = [x.float().contiguous() for x in xs], _geom(xs)
+        C, dev = xs[0].shape[-1], xs[0].device
+        n, K = len(geom), k * C
         w = weight.detach().float().contiguous()
         N = w.shape[1]
         fused = act and N % 4 == 0 and N <= 1024
         kcat = fused and knobs.get("VMASR_MPD_KCAT")
-        with torch.cuda.device(dev):
-            if kcat:
-                # (opt-in, VMASR_MPD_KCAT=1 — measured SLOWER in round 3: 38.8 vs 38.0 ms per step.  The epilogue gains 0.36 ms
-                #  (one partial product to read instead of three), but im2col writes a third operand block (+0.25 ms) and
-                #  hipBLASLt's kernels for K' = 3K with M = 4.7k .. 36k are slower than three K-sized products (+0.9 ms).)
-                # ONE operand [hi | lo | hi] (n, rows, 3K): the forward triple as a single GEMM over the concatenated contraction;
-                # hi / lo stay addressable as column blocks (ld = 3K) for the weight-gradient GEMMs
-                acat = torch.empty((n, rows, 3 * K), dtype=torch.bfloat16, device=dev)
-                _lib.check(lib.vmasr_im2col_kx1_split3_multi(ptrs, Ns, Hs, n, acat.data_ptr(), C, k, stride, pad, rows,
-                                                             _lib.current_stream(dev)), "im2col_kx1_split3_multi")
-                ch, cl = acat[:, :, :K], acat[:, :, K:2 * K]
-            else:
-                ch = torch.empty((n, rows, K), dtype=torch.bfloat16, device=dev)
-                cl = torch.empty((n, rows, K), dtype=torch.bfloat16, device=dev)
-                _lib.check(lib.vmasr_im2col_kx1_split_multi(ptrs, Ns, Hs, n, ch.data_ptr(), cl.data_ptr(), C, k, stride, pad, rows,
-                                                            _lib.current_stream(dev)), "im2col_kx1_split_multi")
+        if kcat:
+            # (opt-in, VMASR_MPD_KCAT=1 — measured SLOWER in round 3: 38.8 vs 38.0 ms per step.  The epilogue gains 0.36 ms
+            #  (one partial product to read instead of three), but im2col writes a third operand block (+0.25 ms) and
+            #  hipBLASLt's kernels for K' = 3K with M = 4.7k .. 36k are slower than three K-sized products (+0.9 ms).)
+            # ONE operand [hi | lo | hi] (n, rows, 3K): the forward triple as a single GEMM over the concatenated contraction;
+            # hi / lo stay addressable as column blocks (ld = 3K) for the weight-gradient GEMMs
+            acat = bind.im2col_kx1_split(src, geom, C, k, stride, pad, rows, cat3=True)
+            ch, cl = acat[:, :, :K], acat[:, :, K:2 * K]
+        else:
+            ch, cl = bind.im2col_kx1_split(src, geom, C, k, stride, pad, rows)
         # weights: one pass to the (n, K, 3N) bf16 operand [hi^T | hi^T | lo^T] (csrc/split.hip): column blocks 0 and 2 are
         # the forward B operands; all of it, transposed, is the [wh; wh; wl] operand of the column-gradient GEMM
         # (kept as the transpose of a contiguous tensor: hipBLASLt's kernels for that layout are ~9 % faster here)
-        with torch.cuda.device(dev):
-            wcat = torch.empty((n, K, 3 * N), dtype=torch.bfloat16, device=dev)
-            _lib.check(lib.vmasr_weight_prep_split(w.data_ptr(), wcat.data_ptr(), n, N, K, _lib.current_stream(dev)), "weight_prep_split")
+        wcat = bind.weight_prep_split(w)
         wth, wtl = wcat[:, :, :N], wcat[:, :, 2 * N:]
         b32 = bias.detach().float().contiguous()
         pre = None
@@ -723,9 +567,7 @@ class _StackedConvSplitFn(torch.autograd.Function):
             with torch.cuda.device(dev):
                 wk = torch.cat((wth, wth, wtl), dim=1)                       # (n, 3K, N) = [w_hi^T; w_hi^T; w_lo^T]
                 pre = torch.bmm(acat, wk, out_dtype=f32)
-                y = torch.empty_like(pre)
-                _lib.check(lib.vmasr_bias_gelu_fwd(pre.data_ptr(), b32.data_ptr(), y.data_ptr(), n, rows, N, 1,
-                                                   _lib.current_stream(dev)), "bias_gelu_fwd")
+                y = bind.bias_gelu_fwd(pre, b32)
         elif fused:
             # the three products side by side; the epilogue sums them, adds the bias (-> pre, in place in part 0) and applies GELU
             f32 = torch.float32
@@ -735,9 +577,7 @@ class _StackedConvSplitFn(torch.autograd.Function):
                 torch.bmm(cl, wth, out_dtype=f32, out=parts[1])
                 torch.bmm(ch, wtl, out_dtype=f32, out=parts[2])
                 pre = parts[0]
-                y = torch.empty_like(pre)
-                _lib.check(lib.vmasr_bias_gelu_fwd(parts.data_ptr(), b32.data_ptr(), y.data_ptr(), n, rows, N, 3,
-                                                   _lib.current_stream(dev)), "bias_gelu_fwd")
+                y = bind.bias_gelu_fwd(parts, b32, 3)
         else:
             y = _bmm3(ch, cl, wth, wtl)
             y.add_(b32.unsqueeze(1))
@@ -745,8 +585,7 @@ class _StackedConvSplitFn(torch.autograd.Function):
                 pre = y
                 y = F.gelu(pre)
         ctx.save_for_backward(ch, cl, wcat, *([pre] if pre is not None else []))
-        ctx.geom = (k, stride, pad, [tuple(x.shape) for x in xs], weight.dtype, bias.dtype, [x.dtype for x in xs], act, fused,
-                    tuple(geom) if geom is not None else None)
+        ctx.geom = (k, stride, pad, [tuple(x.shape) for x in xs], weight.dtype, bias.dtype, [x.dtype for x in xs], act, fused, sgeom)
         return y
 
     @staticmethod
@@ -756,24 +595,14 @@ class _StackedConvSplitFn(torch.autograd.Function):
         gy = gy.float().contiguous()
         n, M, N = gy.shape
         K = ch.shape[2]
-        lib = _lib.lib()
         want_db = ctx.needs_input_grad[7] and not _PHASE["skip_weight_grads"]
         want_dx = any(ctx.needs_input_grad[8:])
         db32 = gcat = None
         if N % 4 == 0 and N <= 1024:
             # one pass: (GELU' *) gradient -> bf16 split (+ bias gradient); the fp32 gradient is never written
-            with torch.cuda.device(gy.device):
-                db32, = _lib.zeros_f32(gy.device, (n, N) if want_db else None)
-                if want_dx:    # [gh | gl | gh]: the weight-gradient GEMMs read gh, gl as column blocks of it (lda = 3N)
-                    gcat = torch.empty((n, M, 3 * N), dtype=torch.bfloat16, device=gy.device)
-                    gh, gl = gcat[:, :, :N], gcat[:, :, N:2 * N]
-                else:
-                    gh = torch.empty((n, M, N), dtype=torch.bfloat16, device=gy.device)
-                    gl = torch.empty((n, M, N), dtype=torch.bfloat16, device=gy.device)
-                _lib.check(lib.vmasr_gelu_bwd_split(rest[0].data_ptr() if act else None, gy.data_ptr(),
-                                                    None if want_dx else gh.data_ptr(), None if want_dx else gl.data_ptr(),
-                                                    gcat.data_ptr() if want_dx else None, db32.data_ptr() if want_db else None,
-                                                    n, M, N, _lib.current_stream(gy.device)), "gelu_bwd_split")
+            # (with an input gradient wanted as [gh | gl | gh]: the weight-gradient GEMMs read gh, gl as column blocks of it, lda = 3N)
+            db32, = _lib.zeros_f32(gy.device, (n, N) if want_db else None)
+            gh, gl, gcat = bind.gelu_bwd_split(rest[0] if act else None, gy, db32, cat=want_dx)
         else:
             if act:
                 gy = torch.ops.aten.gelu_backward(gy, rest[0])
@@ -785,20 +614,9 @@ class _StackedConvSplitFn(torch.autograd.Function):
                 gcat = torch.cat((gh, gl, gh), dim=2)
             dcols = torch.bmm(gcat, wcat.transpose(1, 2), out_dtype=torch.float32)
             if sgeom is not None:      # stacked input: its stacked gradient in one launch (zero rows below each slot's data)
-                with torch.cuda.device(gy.device):
-                    dxs_ = torch.empty(shapes[0], dtype=torch.float32, device=gy.device)
-                    _, Ns, Hs = _slot_arrays([0] * n, [N for N, _ in sgeom], [H for _, H in sgeom])
-                    _lib.check(lib.vmasr_col2im_kx1_stacked(dcols.data_ptr(), dxs_.data_ptr(), Ns, Hs, n, shapes[0][2], k, stride, pad, M,
-                                                            shapes[0][1], _lib.F32, _lib.current_stream(gy.device)), "col2im_kx1_stacked")
-                dxs = [dxs_.to(xdts[0])]
-        if want_dx and sgeom is None:
-            with torch.cuda.device(gy.device):
-                outs = [torch.empty(shp, dtype=torch.float32, device=gy.device) if ctx.needs_input_grad[8 + i] else None
-                        for i, shp in enumerate(shapes)]
-                ptrs, Ns, Hs = _slot_arrays([o.data_ptr() if o is not None else 0 for o in outs],
-                                            [B * P for B, P, _, _ in shapes], [H for _, _, H, _ in shapes])
-                _lib.check(lib.vmasr_col2im_kx1_multi(dcols.data_ptr(), ptrs, Ns, Hs, n, shapes[0][3], k, stride, pad, M, _lib.F32,
-                                                      _lib.current_stream(gy.device)), "col2im_kx1_multi")
+                dxs = [bind.col2im_kx1_stacked(dcols, sgeom, shapes[0], k, stride, pad).to(xdts[0])]
+            else:
+                outs = bind.col2im_kx1_multi(dcols, shapes, k, stride, pad, ctx.needs_input_grad[8:])
                 dxs = [o.to(xdts[i]) if o is not None else None for i, o in enumerate(outs)]
         dw = db = None
         if not _PHASE["skip_weight_grads"]:
@@ -890,7 +708,6 @@ class _StackedConvMfmaFn(torch.autograd.Function):
         k, stride, pad, geom, ops, wdt, bdt, xshape = ctx.meta
         n, M, N = gy.shape
         C = xshape[2]
-        lib = _lib.lib()
         skip_w = _PHASE["skip_weight_grads"]
         want_db = ctx.needs_input_grad[8] and not skip_w
         # The input gradient of the 32 -> 128 layer stays FP32 arithmetic: it is the last GEMM in front of d(loss)/d(wave), a sum with heavy
@@ -907,35 +724,20 @@ class _StackedConvMfmaFn(torch.autograd.Function):
             db32 = ctx.link.pop("stash_db", None)
             if (want_db and db32 is None) or (need_pair and gh is None) or (fp32_dgrad and gx is None):
                 raise RuntimeError("MPD: the fused activation backward left less than this layer's backward needs")
-        with torch.cuda.device(gy.device):
-            if stash is None:
-                gy = gy.float().contiguous()
-                db32, = _lib.zeros_f32(gy.device, (n, N) if want_db else None)
-            if stash is not None:
-                pass
-            elif need_pair:
-                gh = torch.empty((n, M, N), dtype=torch.bfloat16, device=gy.device)
-                gl = torch.empty((n, M, N), dtype=torch.bfloat16, device=gy.device)
-                _lib.check(lib.vmasr_gelu_bwd_split(pre.data_ptr(), gy.data_ptr(), gh.data_ptr(), gl.data_ptr(), None,
-                                                    db32.data_ptr() if want_db else None, n, M, N, _lib.current_stream(gy.device)),
-                           "gelu_bwd_split")
-            if fp32_dgrad and stash is None:
-                gx = torch.empty_like(gy)
-                _lib.check(lib.vmasr_gelu_bwd(pre.data_ptr(), gy.data_ptr(), gx.data_ptr(),
-                                              db32.data_ptr() if (want_db and not need_pair) else None, n, M, N,
-                                              _lib.current_stream(gy.device)), "gelu_bwd")
+        if stash is None:
+            gy = gy.float().contiguous()
+            db32, = _lib.zeros_f32(gy.device, (n, N) if want_db else None)
+            if need_pair:
+                gh, gl, _ = bind.gelu_bwd_split(pre, gy, db32)
+            if fp32_dgrad:
+                gx, _ = bind.gelu_bwd(pre, gy, None if need_pair else db32)
         dx = dw = db = None
         if fp32_dgrad and ctx.f32:
             if "wt32" not in ops:      # (n, Cout, k, C) -> (n, C, k*Cout) fp32: the input gradient's B operand, (tap, output channel) order
                 ops["wt32"] = w.view(n, N, k, C).permute(0, 3, 2, 1).reshape(n, C, k * N).contiguous()
             dx = cg.conv_dgrad_f32(gx, ops["wt32"], geom, k, stride, pad, xshape[1])      # exact-f32 implicit GEMM: no column operand, no col2im
         elif fp32_dgrad:
-            dcols = torch.bmm(gx, w)                                      # (n, M, k*C) fp32
-            with torch.cuda.device(gy.device):
-                dx = torch.empty(xshape, dtype=torch.float32, device=gy.device)
-                _, Ns, Hs = _slot_arrays([0] * n, [ns for ns, _ in geom], [h for _, h in geom])
-                _lib.check(lib.vmasr_col2im_kx1_stacked(dcols.data_ptr(), dx.data_ptr(), Ns, Hs, n, C, k, stride, pad, M, xshape[1], _lib.F32,
-                                                        _lib.current_stream(gy.device)), "col2im_kx1_stacked")
+            dx = bind.col2im_kx1_stacked(torch.bmm(gx, w), geom, xshape, k, stride, pad)      # dcols (n, M, k*C) fp32
         elif ctx.needs_input_grad[9]:
             if "wt" not in ops:      # (n, Cout, k, C) -> (n, C, k*Cout): the dgrad GEMM's B operand, (tap, output channel) order
                 ops["wt"] = split_bf16(w.view(n, N, k, C).permute(0, 3, 2, 1).reshape(n, C, k * N).contiguous())
@@ -977,16 +779,9 @@ class _StackedConvFirstFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, W, bias, *xs):
-        n, dev = len(xs), xs[0].device
-        lib = _lib.lib()
         xcs = [x.float().contiguous() for x in xs]
         w32, b32 = W.detach().float().contiguous(), bias.detach().float().contiguous()
-        ptrs, Ns, Hs = _slot_arrays([x.data_ptr() for x in xcs], [x.shape[0] * x.shape[1] for x in xcs], [x.shape[2] for x in xcs])
-        with torch.cuda.device(dev):
-            pre = torch.empty((n, rows, 32), dtype=torch.float32, device=dev)
-            act = torch.empty((n, rows, 32), dtype=torch.float32, device=dev)
-            _lib.check(lib.vmasr_conv_first_fwd(ptrs, Ns, Hs, n, w32.data_ptr(), b32.data_ptr(), pre.data_ptr(), act.data_ptr(), rows,
-                                                _lib.current_stream(dev)), "conv_first_fwd")
+        pre, act = bind.conv_first_fwd(xcs, _geom(xcs), w32, b32, rows)
         ctx.save_for_backward(pre, w32, *xcs)
         ctx.meta = (W.dtype, bias.dtype, [x.dtype for x in xs], [tuple(x.shape) for x in xs])
         return act
@@ -995,27 +790,15 @@ class _StackedConvFirstFn(torch.autograd.Function):
     def backward(ctx, gy):
         pre, w32, *xcs = ctx.saved_tensors
         wdt, bdt, xdts, shapes = ctx.meta
-        n, rows, _ = pre.shape
-        lib, dev = _lib.lib(), pre.device
         gy = gy.float().contiguous()
         skip_w = _PHASE["skip_weight_grads"]
         want_dw, want_db = ctx.needs_input_grad[1] and not skip_w, ctx.needs_input_grad[2] and not skip_w
         want_dx = any(ctx.needs_input_grad[3:])
-        ptrs, Ns, Hs = _slot_arrays([x.data_ptr() for x in xcs], [x.shape[0] * x.shape[1] for x in xcs], [x.shape[2] for x in xcs])
-        dxs = [None] * n
-        with torch.cuda.device(dev):
-            dcols = torch.empty((n, rows, 5), dtype=torch.float32, device=dev) if want_dx else None
-            dw, db = _lib.zeros_f32(dev, (n, 32, 5) if want_dw else None, (n, 32) if want_db else None)
-            _lib.check(lib.vmasr_conv_first_bwd(ptrs, Ns, Hs, n, w32.data_ptr(), pre.data_ptr(), gy.data_ptr(),
-                                                dcols.data_ptr() if want_dx else None, dw.data_ptr() if want_dw else None,
-                                                db.data_ptr() if want_db else None, rows, _lib.current_stream(dev)), "conv_first_bwd")
-            if want_dx:
-                outs = [torch.empty(shp, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3 + i] else None for i, shp in enumerate(shapes)]
-                optrs, Ns2, Hs2 = _slot_arrays([o.data_ptr() if o is not None else 0 for o in outs], [B * P for B, P, _, _ in shapes],
-                                               [H for _, _, H, _ in shapes])
-                _lib.check(lib.vmasr_col2im_kx1_multi(dcols.data_ptr(), optrs, Ns2, Hs2, n, 1, 5, 3, 2, rows, _lib.F32,
-                                                      _lib.current_stream(dev)), "col2im_kx1_multi")
-                dxs = [o.to(xdts[i]) if o is not None else None for i, o in enumerate(outs)]
+        dxs = [None] * len(xcs)
+        dcols, dw, db = bind.conv_first_bwd(xcs, _geom(shapes), w32, pre, gy, want_dx, want_dw, want_db)
+        if want_dx:
+            outs = bind.col2im_kx1_multi(dcols, shapes, 5, 3, 2, ctx.needs_input_grad[3:])
+            dxs = [o.to(xdts[i]) if o is not None else None for i, o in enumerate(outs)]
         return (None, dw.to(wdt) if want_dw else None, db.to(bdt) if want_db else None, *dxs)
 
 
@@ -1027,36 +810,20 @@ class _StackedConvPostFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Ms, Hs, W, bias, x):
-        import ctypes
-        n, rows, C = x.shape
-        lib, dev = _lib.lib(), x.device
         xc, w32, b32 = x.contiguous(), W.detach().float().contiguous(), bias.detach().float().contiguous()
-        ms, hs = (ctypes.c_int64 * n)(*Ms), (ctypes.c_int32 * n)(*Hs)
-        with torch.cuda.device(dev):
-            y = torch.empty((n, rows, 1), dtype=torch.float32, device=dev)
-            _lib.check(lib.vmasr_conv_post_fwd(xc.data_ptr(), w32.data_ptr(), b32.data_ptr(), y.data_ptr(), ms, hs, n, rows, C, 3,
-                                               _lib.current_stream(dev)), "conv_post_fwd")
+        y = bind.conv_post_fwd(xc, w32, b32, Ms, Hs)
         ctx.save_for_backward(xc, w32)
         ctx.meta = (tuple(Ms), tuple(Hs), W.dtype, bias.dtype, tuple(bias.shape))
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        import ctypes
         xc, w32 = ctx.saved_tensors
         Ms, Hs, wdt, bdt, bshape = ctx.meta
-        n, rows, C = xc.shape
-        lib, dev = _lib.lib(), xc.device
         gy = gy.float().contiguous()
         skip_w = _PHASE["skip_weight_grads"]
         want_dx, want_dw, want_db = ctx.needs_input_grad[4], ctx.needs_input_grad[2] and not skip_w, ctx.needs_input_grad[3] and not skip_w
-        ms, hs = (ctypes.c_int64 * n)(*Ms), (ctypes.c_int32 * n)(*Hs)
-        with torch.cuda.device(dev):
-            dx = torch.empty_like(xc) if want_dx else None
-            dw, db = _lib.zeros_f32(dev, (n, 1, 3 * C) if want_dw else None, (n,) if want_db else None)
-            _lib.check(lib.vmasr_conv_post_bwd(xc.data_ptr(), w32.data_ptr(), gy.data_ptr(), dx.data_ptr() if want_dx else None,
-                                               dw.data_ptr() if want_dw else None, db.data_ptr() if want_db else None, ms, hs, n, rows, C, 3,
-                                               _lib.current_stream(dev)), "conv_post_bwd")
+        dx, dw, db = bind.conv_post_bwd(xc, w32, gy, Ms, Hs, want_dx, want_dw, want_db)
         return (None, None, dw.to(wdt) if want_dw else None, db.view(bshape).to(bdt) if want_db else None, dx)
 
 
@@ -1074,13 +841,7 @@ class _UnstackRowsFn(torch.autograd.Function):
     def backward(ctx, *gs):
         ref = next(g for g in gs if g is not None)
         if ref.is_cuda and len(gs) <= 8:
-            with torch.cuda.device(ref.device):
-                full = torch.empty(ctx.shape, dtype=ref.dtype, device=ref.device)
-                gc = [g.contiguous() if g is not None else None for g in gs]
-                ptrs, Ms, _ = _slot_arrays([g.data_ptr() if g is not None else 0 for g in gc], list(ctx.Ms))
-                _lib.check(_lib.lib().vmasr_stack_rows(ptrs, Ms, len(gs), full.data_ptr(), ctx.shape[1],
-                                                       ctx.shape[2] * ref.element_size(), _lib.current_stream(ref.device)), "stack_rows")
-            return (full, *([None] * len(ctx.Ms)))
+            return (bind.stack_rows(gs, ctx.Ms, ctx.shape, ref), *([None] * len(ctx.Ms)))
         full = torch.empty(ctx.shape, dtype=ref.dtype, device=ref.device)
         for i, (g, m) in enumerate(zip(gs, ctx.Ms)):
             if g is None:
@@ -1122,7 +883,6 @@ class _FeatTapFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, gtok):
-        import ctypes
         h = ctx.holder
         sgn = h.get("sgn")          # (kept: with a shared discriminator pass the graph is walked once per loss phase)
         h.pop("gtok", None)         # (left by the loss' backward for the layer above: _StackedConvMfmaFn._fuse_below)
@@ -1130,18 +890,8 @@ class _FeatTapFn(torch.autograd.Function):
             return gy, None
         if gtok is None or sgn is None:
             return gy, None
-        valid, scale = h["valid"], h["scale"]
-        n, rows_g, N = sgn.shape
-        v = (ctypes.c_int64 * n)(*valid)
-        sc = (ctypes.c_float * n)(*scale)
         add = None if gy is None else gy.float().contiguous()
-        gtok = gtok.float().contiguous()
-        with torch.cuda.device(sgn.device):
-            out = torch.empty((n, rows_g, N), dtype=torch.float32, device=sgn.device)
-            _lib.check(_lib.lib().vmasr_masked_l1_bwd_add(sgn.data_ptr(), gtok.data_ptr(), add.data_ptr() if add is not None else None,
-                                                          out.data_ptr(), v, sc, n, rows_g, N, _lib.current_stream(sgn.device)),
-                       "masked_l1_bwd_add")
-        return out, None
+        return bind.masked_l1_bwd(sgn, gtok.float().contiguous(), h["valid"], h["scale"], add, tap=True), None
 
 
 _FEAT_MASKS = {}
@@ -1156,18 +906,8 @@ class _MaskedL1Fn(torch.autograd.Function):
     def forward(ctx, real, gen, valid, scale, token, holder):
         """token / holder: of the map's _FeatTapFn — then `gen` is the DETACHED map, the gradient goes to the token and the
         tap forms the map's gradient from the sign left in `holder`."""
-        import ctypes
-        n, rows_g, N = gen.shape
-        lib, dev = _lib.lib(), gen.device
-        nb = lib.vmasr_masked_l1_blocks()
-        v = (ctypes.c_int64 * n)(*valid)
-        sc = (ctypes.c_float * n)(*scale)
         tapped = token is not None and ctx.needs_input_grad[4]
-        with torch.cuda.device(dev):
-            partials = torch.empty(n * nb, dtype=torch.float64, device=dev)
-            sgn = torch.empty((n, rows_g, N), dtype=torch.int8, device=dev) if (ctx.needs_input_grad[1] or tapped) else None
-            _lib.check(lib.vmasr_masked_l1_fwd(real.data_ptr(), gen.data_ptr(), sgn.data_ptr() if sgn is not None else None,
-                                               partials.data_ptr(), v, sc, n, real.shape[1], rows_g, N, _lib.current_stream(dev)), "masked_l1_fwd")
+        partials, sgn = bind.masked_l1_fwd(real, gen, valid, scale, ctx.needs_input_grad[1] or tapped)
         ctx.meta = (valid, scale, gen.shape)
         ctx.tapped = tapped
         ctx.holder = holder if tapped else None
@@ -1179,22 +919,14 @@ class _MaskedL1Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         if ctx.tapped:
             # this node runs before the discriminator's layers (it was created after them); the layer above the tapped map folds
             # g * scale * sign into its input-gradient epilogue when it finds the upstream gradient here (_fuse_below)
             ctx.holder["gtok"] = g.detach().reshape(1).float().contiguous()
             return None, None, None, None, g.reshape(1), None
         (sgn,) = ctx.saved_tensors
-        valid, scale, (n, rows_g, N) = ctx.meta
-        v = (ctypes.c_int64 * n)(*valid)
-        sc = (ctypes.c_float * n)(*scale)
-        g = g.float().contiguous()
-        with torch.cuda.device(sgn.device):
-            dgen = torch.empty((n, rows_g, N), dtype=torch.float32, device=sgn.device)
-            _lib.check(_lib.lib().vmasr_masked_l1_bwd(sgn.data_ptr(), g.data_ptr(), dgen.data_ptr(), v, sc, n, rows_g, N,
-                                                      _lib.current_stream(sgn.device)), "masked_l1_bwd")
-        return None, dgen, None, None, None, None
+        valid, scale, _ = ctx.meta
+        return None, bind.masked_l1_bwd(sgn, g.float().contiguous(), valid, scale), None, None, None, None
 
 
 def _masked_l1_ok(yr, yg):
@@ -1233,6 +965,34 @@ def feature_loss_stacked(real, gen):
         term = ((yg[:, :R] - yr[:, :R]).abs() * mask).sum()
         total = term if total is None else total + term
     return total
+
+
+def _layer_path(li, act, cdt, prev_dt, stacked, k, stride, pad, Cin, Cout, n, rows_out, rows_in):
+    """Which implementation one stacked layer of _forward_batched takes: "post" | "first" | "mfma" | "split" | "gemm".
+    act: GELU follows (every layer but conv_post); cdt: compute dtype; prev_dt: dtype of the previous layer's stacked output (None: first
+    layer); stacked: the layer reads that output as it is; rows_out / rows_in: the largest slot's rows.  No tensor: runs without a GPU."""
+    f32 = cdt == torch.float32
+    if (not act and prev_dt is not None and f32 and k == 3 and stride == 1 and pad == 1 and Cout == 1
+            and prev_dt == torch.float32 and knobs.get("VMASR_CONV_POST") and bind.conv_post_supported(Cin, k)):
+        return "post"       # the 1-channel output convolution (csrc/convpost.hip)
+    if (act and li == 0 and f32 and k == 5 and stride == 3 and pad == 2 and Cout == 32 and k * Cin == 5 and Cin == 1
+            and knobs.get("VMASR_CONV_FIRST")):
+        return "first"      # the 1 -> 32 channel input convolution + GELU (csrc/convfirst.hip)
+    if (f32 and knobs.get("VMASR_MPD_GEMM") == "bf16x3" and act and stacked
+            and _batched_conv_mode() == "mfma"
+            and (Cin >= 128 or _l1_mode() != "0")
+            # (shape, slot count and row count of the whole stacked launch: an MPD with more periods or a longer segment than
+            #  the launchers address falls through to the split-GEMM path below)
+            and bind.conv_mfma_supported_launch(Cin, Cout, k, stride, n, max(_round_up(rows_out, 256), rows_in))):
+        # the three compute-bound layers (128 -> 512 -> 1024 -> 1024) as implicit GEMMs (csrc/convgemm.hip).  The 32 -> 128 layer takes the
+        # same kernels in their EXACT-F32 form (VMASR_MPD_CONV_L1=f32, the default: fp32 operands, forward and input gradient; the weight
+        # gradient as a bf16x3 triple): it is the first GEMM behind the signal, and with its forward at the pair's 16-17 bits (=1) the input
+        # gradient d(loss)/d(wave) of an |f|-type loss moved to 2.5e-3 of its scale from float64 (fp32: 4e-4; gate 5e-4, tests/test_mpd.py).
+        # =0: im2col + fp32 library GEMM + bias / GELU pass; GEMM + col2im
+        return "mfma"
+    if _split_mode(k * Cin, Cout, cdt) and Cin % 4 == 0:
+        return "split"      # im2col as bf16 pairs + bf16x3 library GEMMs
+    return "gemm"           # im2col + one batched library GEMM
 
 
 class PeriodDiscriminator(nn.Module):
@@ -1350,42 +1110,26 @@ class MultiPeriodDiscriminator(nn.Module):
             prev_link, this_link = this_link, None   # set by an MFMA layer: the layer above may finish its activation backward
             if stacks and stacks[-1].dtype == cdt and knobs.get("VMASR_STACK_INPUT"):
                 sgeom, src = tuple((B * p, c.shape[2]) for c, p in zip(cur, P)), (stacks[-1],)
-            if (not act and stacks and cdt == torch.float32 and k == 3 and stride == 1 and pad == 1 and W.shape[1] == 1
-                    and stacks[-1].dtype == torch.float32 and knobs.get("VMASR_CONV_POST")
-                    and _lib.lib().vmasr_conv_post_supported(stacks[-1].shape[2], k)):
-                # the 1-channel output convolution straight on the previous layer's stacked maps (no column operand)
+            rows = _round_up(max(Ms), 256)
+            path = _layer_path(li, act, cdt, stacks[-1].dtype if stacks else None, sgeom is not None, k, stride, pad, cur[0].shape[3],
+                               W.shape[1], n, max(Ms), max(B * p * c.shape[2] for c, p in zip(cur, P)))
+            if path == "post":      # straight on the previous layer's stacked maps (no column operand)
                 y = _StackedConvPostFn.apply(tuple(valid[-1]), tuple(c.shape[2] for c in cur), W, bstack, stacks[-1])
-            elif (act and li == 0 and cdt == torch.float32 and k == 5 and stride == 3 and pad == 2 and W.shape[1] == 32 and W.shape[2] == 5
-                  and all(c.shape[3] == 1 for c in cur) and knobs.get("VMASR_CONV_FIRST")):
-                # the 1 -> 32 channel input convolution + GELU straight from the folded signals (no 5-column operand / K = 5 GEMM)
-                y = _StackedConvFirstFn.apply(_round_up(max(Ms), 256), W, bstack, *cur)
-            elif (cdt == torch.float32 and knobs.get("VMASR_MPD_GEMM") == "bf16x3" and act and sgeom is not None
-                  and _batched_conv_mode() == "mfma"
-                  and (cur[0].shape[3] >= 128 or _l1_mode() != "0")
-                  # (shape, slot count and row count of the whole stacked launch: an MPD with more periods or a longer segment than
-                  #  the launchers address falls through to the split-GEMM path below)
-                  and _lib.lib().vmasr_conv_mfma_supported_launch(cur[0].shape[3], W.shape[1], k, stride, n,
-                                                                  max(_round_up(max(Ms), 256), max(g[0] * g[1] for g in sgeom)))):
-                # the three compute-bound layers (128 -> 512 -> 1024 -> 1024): one implicit-GEMM launch each way (csrc/convgemm.hip); the
-                # layer's epilogue leaves the bf16 pair of its activation for the next layer.  The 32 -> 128 layer takes the same kernels
-                # in their EXACT-F32 form (round 6, VMASR_MPD_CONV_L1=f32, the default: fp32 operands, v_mfma_f32_32x32x2_f32, forward and
-                # input gradient; the weight gradient as a bf16x3 triple): it is the first GEMM behind the signal, and with its forward at
-                # the pair's 16-17 bits (VMASR_MPD_CONV_L1=1) the input gradient d(loss)/d(wave) of an |f|-type loss moved to 2.5e-3 of its
-                # scale from float64 (fp32: 4e-4; gate 5e-4, tests/test_mpd.py) — near-zero GELU outputs change sign.  =0: the round-5
-                # path (im2col + fp32 library GEMM + bias / GELU pass; GEMM + col2im)
+            elif path == "first":   # straight from the folded signals (no 5-column operand / K = 5 GEMM)
+                y = _StackedConvFirstFn.apply(rows, W, bstack, *cur)
+            elif path == "mfma":    # one implicit-GEMM launch each way; the epilogue leaves the bf16 pair of its activation for the next layer
                 wcache = None
                 if self._frozen is not None:
                     wcache = self._frozen.setdefault(("mfma_ops", li), {})
                 out_pair = []
                 xh, xl = pair if pair is not None else (None, None)
                 link = {}
-                y = _StackedConvMfmaFn.apply(k, stride, pad, _round_up(max(Ms), 256), sgeom, wcache, out_pair, W, bstack, src[0], xh, xl,
-                                             link, prev_link)
+                y = _StackedConvMfmaFn.apply(k, stride, pad, rows, sgeom, wcache, out_pair, W, bstack, src[0], xh, xl, link, prev_link)
                 next_pair, this_link = out_pair[0], link
-            elif _split_mode(W.shape[2], W.shape[1], cdt) and cur[0].shape[3] % 4 == 0:
-                y = _StackedConvSplitFn.apply(k, stride, pad, _round_up(max(Ms), 256), act, sgeom, W, bstack, *src)
+            elif path == "split":
+                y = _StackedConvSplitFn.apply(k, stride, pad, rows, act, sgeom, W, bstack, *src)
             else:
-                cols = _StackedIm2ColFn.apply(k, stride, pad, _round_up(max(Ms), 256), sgeom, *src)
+                cols = _StackedIm2ColFn.apply(k, stride, pad, rows, sgeom, *src)
                 y = _BatchedLinearFn.apply(cols, W, bstack, cdt, act)
             tap = None
             if (act and y.requires_grad and y.dtype == torch.float32 and x.requires_grad
