@@ -104,3 +104,51 @@ def test_conv_mfma_launch_capability_covers_the_launchers_bounds():
     assert q(1024, 1024, 5, 1, 8, 100_000) == 1 and q(1024, 1024, 5, 1, 9, 100_000) == 0    # wgrad: 8 slots
     assert q(128, 512, 5, 3, 5, (1 << 31) // (5 * 512)) == 0 and q(128, 512, 5, 3, 5, (1 << 31) // (5 * 512) - 1) == 1
     assert q(100, 512, 5, 3, 5, 1000) == 0 and q(128, 512, 5, 3, 0, 1000) == 0
+
+
+class _FakeEntry:
+    """Stand-in for a library entry point: records the arguments _lib.call hands it and returns a chosen code."""
+    __name__ = "vmasr_fake_op"
+
+    def __init__(self, code=0):
+        self.code, self.calls = code, []
+
+    def __call__(self, *args):
+        self.calls.append(args)
+        return self.code
+
+
+def test_lib_call_needs_gpu_tensors_and_a_device():
+    from vm_asr_amd import _lib
+    fn = _FakeEntry()
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        _lib.call(fn, torch.zeros(4), 3)
+    with pytest.raises(RuntimeError, match="fake_op"):   # nothing says where to launch
+        _lib.call(fn, 3, 0.5, None)
+    assert fn.calls == []
+
+
+@pytest.mark.gpu
+def test_lib_call_converts_arguments_and_launches_on_the_current_stream():
+    from vm_asr_amd import _lib
+    _lib.lib()
+    t = torch.zeros(4, device="cuda:0")
+    p = _lib.SScanParams()
+    p.batch = 7
+    fn = _FakeEntry()
+    s = torch.cuda.Stream(device=t.device)
+    assert s.cuda_stream != torch.cuda.current_stream(t.device).cuda_stream
+    with torch.cuda.stream(s):
+        assert _lib.call(fn, t, None, p, 5, 0.25) is None
+    (a_t, a_none, a_p, a_int, a_float, a_stream), = fn.calls
+    assert isinstance(a_t, ctypes.c_void_p) and a_t.value == t.data_ptr()
+    assert a_none is None
+    assert ctypes.cast(a_p, ctypes.POINTER(_lib.SScanParams)).contents.batch == 7      # by reference: the caller's struct, not a copy
+    p.batch = 9
+    assert ctypes.cast(a_p, ctypes.POINTER(_lib.SScanParams)).contents.batch == 9
+    assert type(a_int) is int and a_int == 5 and type(a_float) is float and a_float == 0.25
+    assert isinstance(a_stream, ctypes.c_void_p) and a_stream.value == s.cuda_stream
+    _lib.call(fn, p, device=t.device)                                                 # no tensor: the device is named
+    assert len(fn.calls) == 2 and len(fn.calls[1]) == 2
+    with pytest.raises(RuntimeError, match=r"^fake_op failed \(-3\)"):
+        _lib.call(_FakeEntry(-3), t)

@@ -267,6 +267,33 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def call(fn, *args, device=None):
+    """Launch the entry point `fn`: fn(*args, stream) under the device guard, on the current stream of `device` (default: the device
+    of the first tensor argument; the struct-based and raw-address entry points have none and name it).  Tensors go in as their
+    device pointers and must be on the GPU (contiguity is the caller's business: some entry points take strides), None stays None
+    (an absent optional operand), a ctypes.Structure goes by reference, everything else as it is.  Non-zero raises RuntimeError
+    with vmasr_last_error, labelled with the symbol less its prefix."""
+    import torch
+    what = fn.__name__[len("vmasr_"):]
+    conv = list(args)
+    for i, a in enumerate(conv):
+        t = type(a)
+        if t is int or t is float or a is None:       # (numbers and absent operands: no isinstance needed)
+            continue
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                require_cuda(what, a)
+            if device is None:
+                device = a.device
+            conv[i] = ctypes.c_void_p(a.data_ptr())
+        elif isinstance(a, ctypes.Structure):
+            conv[i] = ctypes.byref(a)
+    if device is None:
+        raise RuntimeError(f"{what}: no tensor argument and no device= to launch on")
+    with torch.cuda.device(device):
+        check(fn(*conv, current_stream(device)), what)
+
+
 def require_cuda(name, *tensors):
     if not all(t.is_cuda for t in tensors):
         raise RuntimeError(f"{name}: expected a CUDA (HIP) tensor; vm_asr_amd has no CPU path")

@@ -67,25 +67,23 @@ def out_positions(H, k, stride, pad):
 def _fwd(fn, xh, xl, wh, wl, bias, geom, k, stride, pad, rows_out, act, want_pair):
     _need(xh, xl, wh, wl, bias)
     (n, _, Cin), Cout, dev = xh.shape, wh.shape[1], xh.device
-    with torch.cuda.device(dev):
-        pre = torch.empty((n, rows_out, Cout), dtype=torch.float32, device=dev)
-        y = torch.empty_like(pre) if act else None
-        yh = torch.empty((n, rows_out, Cout), dtype=torch.bfloat16, device=dev) if act and want_pair else None
-        yl = torch.empty_like(yh) if yh is not None else None
-        sl = _slots(geom, ah=xh, al=xl, bh=wh, bl=wl, c0=pre, c1=y, ch=yh, cl=yl, bias=bias)
-        _apply_limit(Cin, Cout)
-        _lib.check(fn(sl, n, Cin, Cout, k, stride, pad, rows_out, int(bool(act)), _lib.current_stream(dev)), fn.__name__[6:])
+    pre = torch.empty((n, rows_out, Cout), dtype=torch.float32, device=dev)
+    y = torch.empty_like(pre) if act else None
+    yh = torch.empty((n, rows_out, Cout), dtype=torch.bfloat16, device=dev) if act and want_pair else None
+    yl = torch.empty_like(yh) if yh is not None else None
+    sl = _slots(geom, ah=xh, al=xl, bh=wh, bl=wl, c0=pre, c1=y, ch=yh, cl=yl, bias=bias)
+    _apply_limit(Cin, Cout)
+    _lib.call(fn, sl, n, Cin, Cout, k, stride, pad, rows_out, int(bool(act)), device=dev)
     return pre, y, yh, yl
 
 
 def _dgrad(fn, gh, gl, wth, wtl, geom, k, stride, pad, rows_in):
     _need(gh, gl, wth, wtl)
     (n, _, Cout), Cin, dev = gh.shape, wth.shape[1], gh.device
-    with torch.cuda.device(dev):
-        dx = torch.empty((n, rows_in, Cin), dtype=torch.float32, device=dev)
-        sl = _slots(geom, ah=gh, al=gl, bh=wth, bl=wtl, c0=dx)
-        _apply_limit(Cin, Cout)
-        _lib.check(fn(sl, n, Cin, Cout, k, stride, pad, rows_in, _lib.current_stream(dev)), fn.__name__[6:])
+    dx = torch.empty((n, rows_in, Cin), dtype=torch.float32, device=dev)
+    sl = _slots(geom, ah=gh, al=gl, bh=wth, bl=wtl, c0=dx)
+    _apply_limit(Cin, Cout)
+    _lib.call(fn, sl, n, Cin, Cout, k, stride, pad, rows_in, device=dev)
     return dx
 
 
@@ -129,21 +127,20 @@ def conv_dgrad_gelu(gh, gl, wth, wtl, geom, k, stride, pad, rows_in, pre, want_f
     (n, _, Cout), Cin, dev = gh.shape, wth.shape[1], gh.device
     assert pre.shape == (n, rows_in, Cin) and pre.dtype == torch.float32 and (want_f32 or want_pair)
     assert sgn is None or (sgn.shape == pre.shape and sgn.dtype == torch.int8 and gtok is not None and gtok.dtype == torch.float32)
-    with torch.cuda.device(dev):
-        g32 = torch.empty((n, rows_in, Cin), dtype=torch.float32, device=dev) if want_f32 else None
-        oh = torch.empty((n, rows_in, Cin), dtype=torch.bfloat16, device=dev) if want_pair else None
-        ol = torch.empty_like(oh) if want_pair else None
-        sl = _slots(geom, ah=gh, al=gl, bh=wth, bl=wtl, c0=g32, ch=oh, cl=ol)
-        ep = (_lib.CgGeluBwd * n)()
-        for i in range(n):
-            ep[i].pre = _ptr(pre, i, rows_in * Cin * 4)
-            ep[i].sgn = _ptr(sgn, i, rows_in * Cin)
-            ep[i].valid = int(valid[i]) if (sgn is not None and valid is not None) else 0
-            ep[i].scale = float(scale[i]) if (sgn is not None and scale is not None) else 0.0
-            ep[i].db = _ptr(db, i, Cin * 4)
-        _apply_limit(Cin, Cout)
-        _lib.check(_lib.lib().vmasr_conv_mfma_dgrad_gelu(sl, ep, ctypes.c_void_p(gtok.data_ptr()) if sgn is not None else None, n, Cin, Cout,
-                                                         k, stride, pad, rows_in, _lib.current_stream(dev)), "conv_mfma_dgrad_gelu")
+    g32 = torch.empty((n, rows_in, Cin), dtype=torch.float32, device=dev) if want_f32 else None
+    oh = torch.empty((n, rows_in, Cin), dtype=torch.bfloat16, device=dev) if want_pair else None
+    ol = torch.empty_like(oh) if want_pair else None
+    sl = _slots(geom, ah=gh, al=gl, bh=wth, bl=wtl, c0=g32, ch=oh, cl=ol)
+    ep = (_lib.CgGeluBwd * n)()
+    for i in range(n):
+        ep[i].pre = _ptr(pre, i, rows_in * Cin * 4)
+        ep[i].sgn = _ptr(sgn, i, rows_in * Cin)
+        ep[i].valid = int(valid[i]) if (sgn is not None and valid is not None) else 0
+        ep[i].scale = float(scale[i]) if (sgn is not None and scale is not None) else 0.0
+        ep[i].db = _ptr(db, i, Cin * 4)
+    _apply_limit(Cin, Cout)
+    _lib.call(_lib.lib().vmasr_conv_mfma_dgrad_gelu, sl, ep, gtok if sgn is not None else None, n, Cin, Cout, k, stride, pad, rows_in,
+              device=dev)
     return g32, ((oh, ol) if want_pair else None)
 
 
@@ -168,12 +165,10 @@ def conv_wgrad(gh, gl, xh, xl, geom, k, stride, pad, splits=None):
     if splits is None:
         M = max(nseq * out_positions(H, k, stride, pad) for nseq, H in geom)
         splits = wgrad_splits(n, Cin, Cout, k, M)
-    with torch.cuda.device(dev):
-        parts = torch.empty((n, splits, Cout, k * Cin), dtype=torch.float32, device=dev)
-        sl = _slots(geom, ah=gh, al=gl, bh=xh, bl=xl, c0=parts)
-        _apply_limit(Cin, Cout)
-        _lib.check(_lib.lib().vmasr_conv_mfma_wgrad(sl, n, Cin, Cout, k, stride, pad, splits, _lib.current_stream(dev)),
-                   "conv_mfma_wgrad")
-        if splits == 1:
-            return parts.view(n, Cout, k * Cin)
+    parts = torch.empty((n, splits, Cout, k * Cin), dtype=torch.float32, device=dev)
+    sl = _slots(geom, ah=gh, al=gl, bh=xh, bl=xl, c0=parts)
+    _apply_limit(Cin, Cout)
+    _lib.call(_lib.lib().vmasr_conv_mfma_wgrad, sl, n, Cin, Cout, k, stride, pad, splits, device=dev)
+    if splits == 1:
+        return parts.view(n, Cout, k * Cin)
     return sum_parts(parts, 1, n, splits, (Cout, k * Cin))

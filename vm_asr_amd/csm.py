@@ -12,7 +12,6 @@ Triton versions do.  Compute: vm_asr_amd/csrc/csm.hip.  No CPU fallback.
 import torch
 
 from . import _lib
-from ._lib import ptr as _p
 
 __all__ = ["cross_scan", "cross_merge", "CrossScan", "CrossMerge", "CrossScanHIP", "CrossMergeHIP", "CrossScanF32"]
 
@@ -23,11 +22,8 @@ def cross_scan(x: torch.Tensor, out_dtype=None) -> torch.Tensor:
     B, C, H, W = x.shape
     x = x.contiguous()
     out_dtype = out_dtype or x.dtype
-    with torch.cuda.device(x.device):
-        xs = torch.empty((B, 4, C, H * W), dtype=out_dtype, device=x.device)
-        _lib.check(_lib.lib().vmasr_cross_scan_cvt(_p(x), _p(xs), B, C, H, W, _lib.torch_dtype_code(x.dtype),
-                                                   _lib.torch_dtype_code(out_dtype), _lib.current_stream(x.device)),
-                   "cross_scan")
+    xs = torch.empty((B, 4, C, H * W), dtype=out_dtype, device=x.device)
+    _lib.call(_lib.lib().vmasr_cross_scan_cvt, x, xs, B, C, H, W, _lib.torch_dtype_code(x.dtype), _lib.torch_dtype_code(out_dtype))
     return xs
 
 
@@ -39,11 +35,8 @@ def cross_merge(ys: torch.Tensor, H: int, W: int, out_dtype=None) -> torch.Tenso
         raise RuntimeError("cross_merge: expected 4 scan directions")
     ys = ys.contiguous()
     out_dtype = out_dtype or ys.dtype
-    with torch.cuda.device(ys.device):
-        y = torch.empty((B, C, H * W), dtype=out_dtype, device=ys.device)
-        _lib.check(_lib.lib().vmasr_cross_merge_cvt(_p(ys), _p(y), B, C, H, W, _lib.torch_dtype_code(ys.dtype),
-                                                    _lib.torch_dtype_code(out_dtype), _lib.current_stream(ys.device)),
-                   "cross_merge")
+    y = torch.empty((B, C, H * W), dtype=out_dtype, device=ys.device)
+    _lib.call(_lib.lib().vmasr_cross_merge_cvt, ys, y, B, C, H, W, _lib.torch_dtype_code(ys.dtype), _lib.torch_dtype_code(out_dtype))
     return y
 
 

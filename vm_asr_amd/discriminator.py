@@ -564,20 +564,18 @@ class _StackedConvSplitFn(torch.autograd.Function):
         pre = None
         if kcat:
             f32 = torch.float32
-            with torch.cuda.device(dev):
-                wk = torch.cat((wth, wth, wtl), dim=1)                       # (n, 3K, N) = [w_hi^T; w_hi^T; w_lo^T]
-                pre = torch.bmm(acat, wk, out_dtype=f32)
-                y = bind.bias_gelu_fwd(pre, b32)
+            wk = torch.cat((wth, wth, wtl), dim=1)                       # (n, 3K, N) = [w_hi^T; w_hi^T; w_lo^T]
+            pre = torch.bmm(acat, wk, out_dtype=f32)
+            y = bind.bias_gelu_fwd(pre, b32)
         elif fused:
             # the three products side by side; the epilogue sums them, adds the bias (-> pre, in place in part 0) and applies GELU
             f32 = torch.float32
-            with torch.cuda.device(dev):
-                parts = torch.empty((3, n, rows, N), dtype=f32, device=dev)
-                torch.bmm(ch, wth, out_dtype=f32, out=parts[0])
-                torch.bmm(cl, wth, out_dtype=f32, out=parts[1])
-                torch.bmm(ch, wtl, out_dtype=f32, out=parts[2])
-                pre = parts[0]
-                y = bind.bias_gelu_fwd(parts, b32, 3)
+            parts = torch.empty((3, n, rows, N), dtype=f32, device=dev)
+            torch.bmm(ch, wth, out_dtype=f32, out=parts[0])
+            torch.bmm(cl, wth, out_dtype=f32, out=parts[1])
+            torch.bmm(ch, wtl, out_dtype=f32, out=parts[2])
+            pre = parts[0]
+            y = bind.bias_gelu_fwd(parts, b32, 3)
         else:
             y = _bmm3(ch, cl, wth, wtl)
             y.add_(b32.unsqueeze(1))

@@ -9,7 +9,6 @@ Compute: vm_asr_amd/csrc/dwconv.hip.  No CPU fallback.
 import torch
 
 from . import _lib
-from ._lib import ptr as _p
 
 __all__ = ["dwconv3x3_silu", "DWConv3x3SiLU"]
 
@@ -25,11 +24,8 @@ class DWConv3x3SiLU(torch.autograd.Function):
         x = x.contiguous()
         w32 = weight.detach().float().contiguous()
         b32 = None if bias is None else bias.detach().float().contiguous()
-        with torch.cuda.device(x.device):
-            y = torch.empty_like(x)
-            _lib.check(_lib.lib().vmasr_dwconv_silu_fwd(_p(x), _p(w32), _p(b32), _p(y), B, C, H, W,
-                                                        _lib.torch_dtype_code(x.dtype),
-                                                        _lib.current_stream(x.device)), "dwconv_silu_fwd")
+        y = torch.empty_like(x)
+        _lib.call(_lib.lib().vmasr_dwconv_silu_fwd, x, w32, b32, y, B, C, H, W, _lib.torch_dtype_code(x.dtype))
         ctx.save_for_backward(x, w32, b32 if b32 is not None else torch.empty(0, device=x.device))
         ctx.has_bias = bias is not None
         ctx.wdtype = weight.dtype
@@ -44,14 +40,11 @@ class DWConv3x3SiLU(torch.autograd.Function):
         gy = gy.contiguous()
         if gy.dtype != x.dtype:
             gy = gy.to(x.dtype)
-        with torch.cuda.device(x.device):
-            dx = torch.empty_like(x)
-            dw, db = _lib.zeros_f32(x.device, (C, 1, 3, 3), (C,) if ctx.has_bias else None)
-            ws = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().vmasr_dwconv_silu_bwd(_p(x), _p(w32), _p(b32) if ctx.has_bias else None, _p(gy),
-                                                        _p(dx), _p(dw), _p(db), _p(ws), B, C, H, W,
-                                                        _lib.torch_dtype_code(x.dtype),
-                                                        _lib.current_stream(x.device)), "dwconv_silu_bwd")
+        dx = torch.empty_like(x)
+        dw, db = _lib.zeros_f32(x.device, (C, 1, 3, 3), (C,) if ctx.has_bias else None)
+        ws = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+        _lib.call(_lib.lib().vmasr_dwconv_silu_bwd, x, w32, b32 if ctx.has_bias else None, gy, dx, dw, db, ws, B, C, H, W,
+                  _lib.torch_dtype_code(x.dtype))
         return dx, dw.to(ctx.wdtype), (db.to(ctx.bdtype) if ctx.has_bias else None)
 
 

@@ -5,8 +5,6 @@ torch's `state_dict` layout, interchangeable with the reference's (utils/optimiz
 This class only replaces `optimizer.step()` in the replayed training step: a device table of (param, grad, exp_avg,
 exp_avg_sq, bf16 shadow) pointers built once, `step` counters advanced by one multi-tensor add, then one kernel.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -103,9 +101,5 @@ class HipAdamWStep:
     @torch.no_grad()
     def step(self):
         torch._foreach_add_(self.steps, 1)
-        dev = self.lr.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().vmasr_adamw_step(self.items.data_ptr(), self.chunks.data_ptr(), self.nchunks, self.total,
-                                                   self.lr.data_ptr(), self.steps[0].data_ptr(), ctypes.c_float(self.betas[0]),
-                                                   ctypes.c_float(self.betas[1]), ctypes.c_float(self.eps), _lib.current_stream(dev)),
-                       "adamw_step")
+        _lib.call(_lib.lib().vmasr_adamw_step, self.items, self.chunks, self.nchunks, self.total, self.lr, self.steps[0], self.betas[0],
+                  self.betas[1], self.eps, device=self.lr.device)

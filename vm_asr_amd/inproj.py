@@ -11,7 +11,6 @@ multiple of 32; `norm` a LayerNorm or nn.Identity.  One launch instead of LayerN
 import torch
 
 from . import _lib, knobs
-from ._lib import ptr as _p
 from . import layernorm as _ln
 from .wgrad import weight_grad_finished
 from .linear import bf16_shadow, bf16_shadow_t
@@ -46,11 +45,9 @@ class _InProjFn(torch.autograd.Function):
         g32 = None if gamma is None else gamma.detach().float().contiguous()
         b32 = None if beta is None else beta.detach().float().contiguous()
         wb = bf16_shadow(weight).contiguous()
-        with torch.cuda.device(x.device):
-            xT = torch.empty((B, 2 * d, H, W), dtype=torch.bfloat16, device=x.device)
-            sz = torch.empty((B, H, W, 2 * d), dtype=torch.bfloat16, device=x.device)
-            _lib.check(_lib.lib().vmasr_inproj_fwd(_p(x2), _p(g32), _p(b32), float(eps), _p(wb), _p(xT), _p(sz), B * L, L, d,
-                                                   _lib.torch_dtype_code(x2.dtype), _lib.current_stream(x.device)), "inproj_fwd")
+        xT = torch.empty((B, 2 * d, H, W), dtype=torch.bfloat16, device=x.device)
+        sz = torch.empty((B, H, W, 2 * d), dtype=torch.bfloat16, device=x.device)
+        _lib.call(_lib.lib().vmasr_inproj_fwd, x2, g32, b32, float(eps), wb, xT, sz, B * L, L, d, _lib.torch_dtype_code(x2.dtype))
         ctx.save_for_backward(x2, g32 if g32 is not None else torch.empty(0, device=x.device),
                               b32 if b32 is not None else torch.empty(0, device=x.device), wb)
         ctx.meta = (x.shape, eps, gamma is not None, None if gamma is None else gamma.dtype, None if beta is None else beta.dtype, weight.dtype)
@@ -75,29 +72,25 @@ class _InProjFn(torch.autograd.Function):
         lib = _lib.lib()
         dxT = (torch.zeros((B, 2 * d, H, W), **bf) if dxT is None else dxT.to(torch.bfloat16)).contiguous()
         dsz = (torch.zeros((B, H, W, 2 * d), **bf) if dsz is None else dsz.to(torch.bfloat16)).contiguous()
-        with torch.cuda.device(dev):
-            wt = ctx.wt if ctx.wt is not None else wb.t().contiguous()
-            dxn = torch.empty((rows, d), **bf)
-            xn = torch.empty((rows, d), **bf)
-            gpre = torch.empty((rows, 4 * d), **bf)
-            stats = torch.empty((2, rows), dtype=torch.float32, device=dev) if has_norm else None
-            _lib.check(lib.vmasr_inproj_bwd(_p(x2), _p(g32) if has_norm else None, _p(b32) if has_norm else None, float(eps), _p(wb), _p(wt),
-                                            _p(dxT), _p(dsz), _p(dxn), _p(xn), _p(gpre), _p(stats[0]) if has_norm else None,
-                                            _p(stats[1]) if has_norm else None, rows, L, d, _lib.torch_dtype_code(x2.dtype),
-                                            _lib.current_stream(dev)), "inproj_bwd")
-            dg = db = None
-            if has_norm:
-                dx = torch.empty_like(x2)
-                dg = torch.empty(d, dtype=torch.float32, device=dev)
-                db = torch.empty(d, dtype=torch.float32, device=dev)
-                ws = torch.empty(lib.vmasr_layer_norm_bwd_workspace(rows, d) // 4, dtype=torch.float32, device=dev)
-                later = (gdt == torch.float32 and bedt == torch.float32 and ctx.fresh() and _ln.defer_reduction(ws, dg, db, rows, d, *ctx.params))
-                _lib.check(lib.vmasr_layer_norm_bwd(_p(x2), _p(dxn), _p(g32), _p(stats[0]), _p(stats[1]), _p(dx), None if later else _p(dg),
-                                                    None if later else _p(db), _p(ws), rows, d, _lib.torch_dtype_code(x2.dtype), _lib.BF16,
-                                                    _lib.current_stream(dev)), "layer_norm_bwd")
-                dg, db = dg.to(gdt), db.to(bedt)
-            else:
-                dx = dxn.to(x2.dtype)
+        wt = ctx.wt if ctx.wt is not None else wb.t().contiguous()
+        dxn = torch.empty((rows, d), **bf)
+        xn = torch.empty((rows, d), **bf)
+        gpre = torch.empty((rows, 4 * d), **bf)
+        stats = torch.empty((2, rows), dtype=torch.float32, device=dev) if has_norm else None
+        _lib.call(lib.vmasr_inproj_bwd, x2, g32 if has_norm else None, b32 if has_norm else None, float(eps), wb, wt, dxT, dsz, dxn, xn, gpre,
+                  stats[0] if has_norm else None, stats[1] if has_norm else None, rows, L, d, _lib.torch_dtype_code(x2.dtype))
+        dg = db = None
+        if has_norm:
+            dx = torch.empty_like(x2)
+            dg = torch.empty(d, dtype=torch.float32, device=dev)
+            db = torch.empty(d, dtype=torch.float32, device=dev)
+            ws = torch.empty(lib.vmasr_layer_norm_bwd_workspace(rows, d) // 4, dtype=torch.float32, device=dev)
+            later = (gdt == torch.float32 and bedt == torch.float32 and ctx.fresh() and _ln.defer_reduction(ws, dg, db, rows, d, *ctx.params))
+            _lib.call(lib.vmasr_layer_norm_bwd, x2, dxn, g32, stats[0], stats[1], dx, dg if not later else None, db if not later else None, ws,
+                      rows, d, _lib.torch_dtype_code(x2.dtype), _lib.BF16)
+            dg, db = dg.to(gdt), db.to(bedt)
+        else:
+            dx = dxn.to(x2.dtype)
         # (4d, d) fp32, split over the rows when few tiles; finished together with the pass' other weight gradients (wgrad.py)
         dw, _ = weight_grad_finished(gpre, xn, d, ctx.wparam, None, _ln.fresh(ctx.wparam))
         return dx.view(shape), dg, db, dw.to(wdt), None

@@ -12,7 +12,6 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import ptr as _p
 
 __all__ = ["LayerNorm", "layer_norm"]
 
@@ -114,16 +113,15 @@ def _flush_pending():
     parts = np.array([i[0].data_ptr() for i in items], dtype=np.uint64)
     dgs, dbs = np.array([i[1][1] for i in items], dtype=np.uint64), np.array([i[2][1] for i in items], dtype=np.uint64)
     nblk, cs = np.array([i[3] for i in items], dtype=np.int32), np.array([i[4] for i in items], dtype=np.int32)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().vmasr_layer_norm_bwd_reduce_multi(parts.ctypes.data, dgs.ctypes.data, dbs.ctypes.data, nblk.ctypes.data,
-                                                                cs.ctypes.data, n, _lib.current_stream(dev)), "layer_norm_bwd_reduce_multi")
-        # autograd normally STEALS the returned gradient tensor as param.grad (fresh .grad, sole owner, contiguous); if it cloned
-        # instead, copy the reduced values over (correct either way; the extra copy only in the unusual case)
-        for _, (gst, gptr), (bst, bptr), _, C, weight, bias in items:
-            for param, st, ptr in ((weight, gst, gptr), (bias, bst, bptr)):
-                if param is None or st is None or param.grad is None or param.grad.data_ptr() == ptr:
-                    continue
-                param.grad.copy_(torch.empty(0, dtype=torch.float32, device=dev).set_(st, 0, (C,)).view_as(param.grad))
+    _lib.call(_lib.lib().vmasr_layer_norm_bwd_reduce_multi, parts.ctypes.data, dgs.ctypes.data, dbs.ctypes.data, nblk.ctypes.data,
+              cs.ctypes.data, n, device=dev)
+    # autograd normally STEALS the returned gradient tensor as param.grad (fresh .grad, sole owner, contiguous); if it cloned
+    # instead, copy the reduced values over (correct either way; the extra copy only in the unusual case)
+    for _, (gst, gptr), (bst, bptr), _, C, weight, bias in items:
+        for param, st, ptr in ((weight, gst, gptr), (bias, bst, bptr)):
+            if param is None or st is None or param.grad is None or param.grad.data_ptr() == ptr:
+                continue
+            param.grad.copy_(torch.empty(0, dtype=torch.float32, device=dev).set_(st, 0, (C,)).view_as(param.grad))
 
 
 def defer_reduction(ws, dg, db, rows, C, weight=None, bias=None, nblk=None):
@@ -148,14 +146,11 @@ class _LayerNormFn(torch.autograd.Function):
         rows = x2.shape[0]
         w32 = None if weight is None else weight.detach().float().contiguous()
         b32 = None if bias is None else bias.detach().float().contiguous()
-        with torch.cuda.device(x.device):
-            y = torch.empty((rows, C), dtype=out_dtype, device=x.device)
-            mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().vmasr_layer_norm_fwd(_p(x2), _p(w32), _p(b32), _p(y), _p(mean), _p(rstd), rows, C,
-                                                       float(eps), _lib.torch_dtype_code(x2.dtype),
-                                                       _lib.torch_dtype_code(out_dtype),
-                                                       _lib.current_stream(x.device)), "layer_norm_fwd")
+        y = torch.empty((rows, C), dtype=out_dtype, device=x.device)
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        _lib.call(_lib.lib().vmasr_layer_norm_fwd, x2, w32, b32, y, mean, rstd, rows, C, float(eps), _lib.torch_dtype_code(x2.dtype),
+                  _lib.torch_dtype_code(out_dtype))
         ctx.save_for_backward(x2, w32 if w32 is not None else torch.empty(0, device=x.device), mean, rstd)
         ctx.meta = (x.shape, weight is not None, bias is not None,
                     None if weight is None else weight.dtype, None if bias is None else bias.dtype)
@@ -177,20 +172,17 @@ class _LayerNormFn(torch.autograd.Function):
         if not gy2.is_contiguous():
             gy2 = gy2.contiguous()
         lib = _lib.lib()
-        with torch.cuda.device(x2.device):
-            dx = torch.empty_like(x2)
-            dg = torch.empty(C, dtype=torch.float32, device=x2.device) if has_w else None
-            db = torch.empty(C, dtype=torch.float32, device=x2.device) if has_b else None
-            ws = None
-            if has_w or has_b:
-                ws = torch.empty(lib.vmasr_layer_norm_bwd_workspace(rows, C) // 4, dtype=torch.float32, device=x2.device)
-            # fp32 parameters whose .grad is still empty: their gradients can be filled at the end of the pass (see DEFER_REDUCE)
-            later = (ws is not None and DEFER_REDUCE and wdt in (None, torch.float32) and bdt in (None, torch.float32) and ctx.fresh()
-                     and defer_reduction(ws, dg, db, rows, C, *ctx.params))
-            _lib.check(lib.vmasr_layer_norm_bwd(_p(x2), _p(gy2), _p(w32) if has_w else None, _p(mean), _p(rstd), _p(dx),
-                                                None if later else _p(dg), None if later else _p(db), _p(ws), rows, C,
-                                                _lib.torch_dtype_code(x2.dtype), _lib.torch_dtype_code(gy2.dtype),
-                                                _lib.current_stream(x2.device)), "layer_norm_bwd")
+        dx = torch.empty_like(x2)
+        dg = torch.empty(C, dtype=torch.float32, device=x2.device) if has_w else None
+        db = torch.empty(C, dtype=torch.float32, device=x2.device) if has_b else None
+        ws = None
+        if has_w or has_b:
+            ws = torch.empty(lib.vmasr_layer_norm_bwd_workspace(rows, C) // 4, dtype=torch.float32, device=x2.device)
+        # fp32 parameters whose .grad is still empty: their gradients can be filled at the end of the pass (see DEFER_REDUCE)
+        later = (ws is not None and DEFER_REDUCE and wdt in (None, torch.float32) and bdt in (None, torch.float32) and ctx.fresh()
+                 and defer_reduction(ws, dg, db, rows, C, *ctx.params))
+        _lib.call(lib.vmasr_layer_norm_bwd, x2, gy2, w32 if has_w else None, mean, rstd, dx, dg if not later else None,
+                  db if not later else None, ws, rows, C, _lib.torch_dtype_code(x2.dtype), _lib.torch_dtype_code(gy2.dtype))
         return (dx.view(shape), dg.to(wdt) if has_w else None, db.to(bdt) if has_b else None, None, None)
 
 

@@ -14,7 +14,6 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, knobs
-from ._lib import ptr as _p
 
 __all__ = ["Linear", "linear"]
 
@@ -29,11 +28,9 @@ class _SmallLinearFn(torch.autograd.Function):
         rows = x2.shape[0]
         w32 = weight.detach().float().contiguous()
         b32 = None if bias is None else bias.detach().float().contiguous()
-        with torch.cuda.device(x.device):
-            y = torch.empty((rows, out_f), dtype=out_dtype, device=x.device)
-            _lib.check(_lib.lib().vmasr_small_linear_fwd(_p(x2), _p(w32), _p(b32), _p(y), rows, in_f, out_f,
-                                                         _lib.torch_dtype_code(x2.dtype), _lib.torch_dtype_code(out_dtype),
-                                                         _lib.current_stream(x.device)), "small_linear_fwd")
+        y = torch.empty((rows, out_f), dtype=out_dtype, device=x.device)
+        _lib.call(_lib.lib().vmasr_small_linear_fwd, x2, w32, b32, y, rows, in_f, out_f, _lib.torch_dtype_code(x2.dtype),
+                  _lib.torch_dtype_code(out_dtype))
         ctx.save_for_backward(x2, w32)
         ctx.meta = (x.shape, weight.dtype, None if bias is None else bias.dtype, x.requires_grad)
         return y.view(*x.shape[:-1], out_f)
@@ -51,15 +48,12 @@ class _SmallLinearFn(torch.autograd.Function):
         if not gy2.is_contiguous():
             gy2 = gy2.contiguous()
         lib = _lib.lib()
-        with torch.cuda.device(x2.device):
-            dx = torch.empty_like(x2) if need_dx else None
-            dw = torch.empty((out_f, in_f), dtype=torch.float32, device=x2.device)
-            db = torch.empty(out_f, dtype=torch.float32, device=x2.device) if bdt is not None else None
-            ws = torch.empty(lib.vmasr_small_linear_bwd_workspace(rows, in_f, out_f) // 4, dtype=torch.float32,
-                             device=x2.device)
-            _lib.check(lib.vmasr_small_linear_bwd(_p(x2), _p(w32), _p(gy2), _p(dx), _p(dw), _p(db), _p(ws), rows, in_f,
-                                                  out_f, _lib.torch_dtype_code(x2.dtype), _lib.torch_dtype_code(gy2.dtype),
-                                                  _lib.current_stream(x2.device)), "small_linear_bwd")
+        dx = torch.empty_like(x2) if need_dx else None
+        dw = torch.empty((out_f, in_f), dtype=torch.float32, device=x2.device)
+        db = torch.empty(out_f, dtype=torch.float32, device=x2.device) if bdt is not None else None
+        ws = torch.empty(lib.vmasr_small_linear_bwd_workspace(rows, in_f, out_f) // 4, dtype=torch.float32, device=x2.device)
+        _lib.call(lib.vmasr_small_linear_bwd, x2, w32, gy2, dx, dw, db, ws, rows, in_f, out_f, _lib.torch_dtype_code(x2.dtype),
+                  _lib.torch_dtype_code(gy2.dtype))
         return (dx.view(shape) if need_dx else None, dw.to(wdt), db.to(bdt) if bdt is not None else None, None)
 
 
@@ -164,11 +158,9 @@ def _skinny(x2, w32, bias32, out_dtype, transposed=False):
         out_f, s_out, s_in = w32.shape[1], w32.stride(1), w32.stride(0)
     else:
         out_f, s_out, s_in = w32.shape[0], w32.stride(0), w32.stride(1)
-    with torch.cuda.device(x2.device):
-        y = torch.empty((rows, out_f), dtype=out_dtype, device=x2.device)
-        _lib.check(_lib.lib().vmasr_skinny_linear(x2.data_ptr(), w32.data_ptr(), None if bias32 is None else bias32.data_ptr(), y.data_ptr(),
-                                                  rows, in_f, out_f, s_out, s_in, _lib.torch_dtype_code(x2.dtype), _lib.torch_dtype_code(out_dtype),
-                                                  _lib.current_stream(x2.device)), "skinny_linear")
+    y = torch.empty((rows, out_f), dtype=out_dtype, device=x2.device)
+    _lib.call(_lib.lib().vmasr_skinny_linear, x2, w32, bias32, y, rows, in_f, out_f, s_out, s_in, _lib.torch_dtype_code(x2.dtype),
+              _lib.torch_dtype_code(out_dtype))
     return y
 
 
@@ -221,10 +213,8 @@ _SplitKLinearFn = _LinearFn   # (tests)
 def _f64acc(x2, w, b):
     """x2 (rows, in) @ w (out, in)^T + b with float64 accumulation (csrc/linear.hip), fp32 tensors."""
     rows, out_f = x2.shape[0], w.shape[0]
-    with torch.cuda.device(x2.device):
-        y = torch.empty((rows, out_f), dtype=torch.float32, device=x2.device)
-        _lib.check(_lib.lib().vmasr_linear_f64acc(_p(x2), _p(w), _p(b), _p(y), rows, out_f, w.shape[1], _lib.current_stream(x2.device)),
-                   "linear_f64acc")
+    y = torch.empty((rows, out_f), dtype=torch.float32, device=x2.device)
+    _lib.call(_lib.lib().vmasr_linear_f64acc, x2, w, b, y, rows, out_f, w.shape[1])
     return y
 
 

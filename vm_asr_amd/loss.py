@@ -13,7 +13,6 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, knobs
-from ._lib import ptr as _p
 from . import stft as _stft
 
 __all__ = ["mae_loss", "mse_loss", "stft_magnitude", "STFTLoss", "MultiResolutionSTFTLoss", "HiFiGANLoss"]
@@ -47,10 +46,9 @@ class _STFTLossFn(torch.autograd.Function):
         rx, ix, ry, iy = (t.float().contiguous() for t in (rx, ix, ry, iy))
         n, dev = rx.numel(), rx.device
         lib = _lib.lib()
-        with torch.cuda.device(dev):
-            partials = torch.empty(int(lib.vmasr_stft_loss_blocks()) * 3, dtype=torch.float64, device=dev)
-            out = torch.empty(4, dtype=torch.float32, device=dev)
-            _lib.check(lib.vmasr_stft_loss_fwd(_p(rx), _p(ix), _p(ry), _p(iy), n, _p(partials), _p(out), _lib.current_stream(dev)), "stft_loss_fwd")
+        partials = torch.empty(int(lib.vmasr_stft_loss_blocks()) * 3, dtype=torch.float64, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        _lib.call(lib.vmasr_stft_loss_fwd, rx, ix, ry, iy, n, partials, out)
         ctx.save_for_backward(rx, ix, ry, iy, out)
         ctx.set_materialize_grads(False)
         return out[0], out[1]
@@ -61,10 +59,8 @@ class _STFTLossFn(torch.autograd.Function):
         dev = rx.device
         g_sc = None if g_sc is None else g_sc.float().reshape(1).contiguous()
         g_ml = None if g_ml is None else g_ml.float().reshape(1).contiguous()
-        with torch.cuda.device(dev):
-            drx, dix = torch.empty_like(rx), torch.empty_like(ix)
-            _lib.check(_lib.lib().vmasr_stft_loss_bwd(_p(rx), _p(ix), _p(ry), _p(iy), rx.numel(), _p(out), _p(g_sc), _p(g_ml), _p(drx), _p(dix),
-                                                      _lib.current_stream(dev)), "stft_loss_bwd")
+        drx, dix = torch.empty_like(rx), torch.empty_like(ix)
+        _lib.call(_lib.lib().vmasr_stft_loss_bwd, rx, ix, ry, iy, rx.numel(), out, g_sc, g_ml, drx, dix)
         return drx, dix, None, None
 
 
@@ -122,9 +118,8 @@ class _LSGANFn(torch.autograd.Function):
         xs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         ns = (ctypes.c_int64 * n)(*[t.numel() for t in ts])
         cs = (ctypes.c_float * n)(*targets)
-        with torch.cuda.device(dev):
-            out = torch.empty(1, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().vmasr_lsgan_fwd(xs, ns, cs, n, _p(out), _lib.current_stream(dev)), "lsgan_fwd")
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        _lib.call(_lib.lib().vmasr_lsgan_fwd, xs, ns, cs, n, out)
         ctx.save_for_backward(*ts)
         ctx.targets = targets
         return out[0]
@@ -134,13 +129,12 @@ class _LSGANFn(torch.autograd.Function):
         ts = ctx.saved_tensors
         n, dev = len(ts), ts[0].device
         g = g.float().reshape(1).contiguous()
-        with torch.cuda.device(dev):
-            ds = [torch.empty_like(t) for t in ts]
-            xs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-            dp = (ctypes.c_void_p * n)(*[d.data_ptr() for d in ds])
-            ns = (ctypes.c_int64 * n)(*[t.numel() for t in ts])
-            cs = (ctypes.c_float * n)(*ctx.targets)
-            _lib.check(_lib.lib().vmasr_lsgan_bwd(xs, dp, ns, cs, n, _p(g), _lib.current_stream(dev)), "lsgan_bwd")
+        ds = [torch.empty_like(t) for t in ts]
+        xs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        dp = (ctypes.c_void_p * n)(*[d.data_ptr() for d in ds])
+        ns = (ctypes.c_int64 * n)(*[t.numel() for t in ts])
+        cs = (ctypes.c_float * n)(*ctx.targets)
+        _lib.call(_lib.lib().vmasr_lsgan_bwd, xs, dp, ns, cs, n, g, device=dev)
         return (None, *ds)
 
 

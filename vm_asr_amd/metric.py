@@ -83,12 +83,9 @@ def _workspace(ws, B, T, device):
 
 def _launch(output, target, hf, acc, ws):
     B, T = output.shape
-    with torch.cuda.device(output.device):
-        ws, _ = _workspace(ws, B, T, output.device)
-        res = torch.empty((B, 4), dtype=torch.float32, device=output.device)
-        _lib.check(_lib.lib().vmasr_metrics(_lib.ptr(output), _lib.ptr(target), _lib.ptr(hf), _lib.ptr(res), _lib.ptr(acc), B, T,
-                                            N_FFT, HOP, _lib.ptr(ws), ws.numel() * 4, _lib.current_stream(output.device)),
-                   "metrics")
+    ws, _ = _workspace(ws, B, T, output.device)
+    res = torch.empty((B, 4), dtype=torch.float32, device=output.device)
+    _lib.call(_lib.lib().vmasr_metrics, output, target, hf, res, acc, B, T, N_FFT, HOP, ws, ws.numel() * 4)
     return res, ws
 
 

@@ -12,7 +12,6 @@ recomputes the forward and produces dxn plus the bf16 operands of the weight-gra
 import torch
 
 from . import _lib, knobs
-from ._lib import ptr as _p
 from . import layernorm as _ln
 from .wgrad import weight_grad_finished
 from .linear import bf16_shadow, bf16_shadow_t
@@ -52,10 +51,8 @@ class _FusedMlpFn(torch.autograd.Function):
         w1b, w2b = bf16_shadow(w1).contiguous(), bf16_shadow(w2).contiguous()
         rps = rows // scale.numel() if scale is not None else 0
         sc = None if scale is None else scale.detach().float().contiguous().view(-1)
-        with torch.cuda.device(x.device):
-            y = torch.empty_like(x2)
-            _lib.check(_lib.lib().vmasr_mlp_fwd(_p(x2), _p(g32), _p(be32), float(eps), _p(w1b), _p(b1f), _p(w2b), _p(b2f), _p(sc), rps,
-                                                _p(y), rows, d, _lib.torch_dtype_code(x2.dtype), _lib.current_stream(x.device)), "mlp_fwd")
+        y = torch.empty_like(x2)
+        _lib.call(_lib.lib().vmasr_mlp_fwd, x2, g32, be32, float(eps), w1b, b1f, w2b, b2f, sc, rps, y, rows, d, _lib.torch_dtype_code(x2.dtype))
         ctx.save_for_backward(x2, g32, be32, w1b, b1f, w2b, sc)
         ctx.wts = (bf16_shadow_t(w1, w1b), bf16_shadow_t(w2, w2b))
         ctx.meta = (x.shape, eps, rps, gamma.dtype, beta.dtype, w1.dtype, b1.dtype, w2.dtype, b2.dtype)
@@ -80,27 +77,24 @@ class _FusedMlpFn(torch.autograd.Function):
         lib = _lib.lib()
         dev = x2.device
         bf = dict(dtype=torch.bfloat16, device=dev)
-        with torch.cuda.device(dev):
-            w1t = ctx.wts[0] if ctx.wts[0] is not None else w1b.t().contiguous()
-            w2t = ctx.wts[1] if ctx.wts[1] is not None else w2b.t().contiguous()
-            dxn = torch.empty((rows, d), **bf)
-            xn_aug = torch.empty((rows, d + 8), **bf)
-            gys = torch.empty((rows, d), **bf)
-            act_aug = torch.empty((rows, hd + 8), **bf)
-            gpre = torch.empty((rows, hd), **bf)
-            stats = torch.empty((2, rows), dtype=torch.float32, device=dev)
-            _lib.check(lib.vmasr_mlp_bwd(_p(x2), _p(gy2), _p(g32), _p(be32), float(eps), _p(w1b), _p(w1t), _p(b1f), _p(w2t), _p(sc), rps,
-                                         _p(dxn), _p(xn_aug), _p(gys), _p(act_aug), _p(gpre), _p(stats[0]), _p(stats[1]), rows, d,
-                                         _lib.torch_dtype_code(x2.dtype), _lib.current_stream(dev)), "mlp_bwd")
-            # dx = gy + LayerNorm'(dxn); dgamma, dbeta  (one launch: csrc/ln.hip with the residual gradient folded in)
-            dx = torch.empty_like(x2)
-            dg_ = torch.empty(d, dtype=torch.float32, device=dev)      # separate tensors: autograd adopts each as a .grad
-            db_ = torch.empty(d, dtype=torch.float32, device=dev)
-            ws = torch.empty(lib.vmasr_layer_norm_bwd_workspace(rows, d) // 4, dtype=torch.float32, device=dev)
-            later = (gdt == torch.float32 and bedt == torch.float32 and ctx.fresh() and _ln.defer_reduction(ws, dg_, db_, rows, d, *ctx.params))
-            _lib.check(lib.vmasr_layer_norm_bwd_res(_p(x2), _p(dxn), _p(g32), _p(stats[0]), _p(stats[1]), _p(gy2), _p(dx),
-                                                    None if later else _p(dg_), None if later else _p(db_), _p(ws), rows, d, _lib.torch_dtype_code(x2.dtype), _lib.BF16, _lib.current_stream(dev)),
-                       "layer_norm_bwd_res")
+        w1t = ctx.wts[0] if ctx.wts[0] is not None else w1b.t().contiguous()
+        w2t = ctx.wts[1] if ctx.wts[1] is not None else w2b.t().contiguous()
+        dxn = torch.empty((rows, d), **bf)
+        xn_aug = torch.empty((rows, d + 8), **bf)
+        gys = torch.empty((rows, d), **bf)
+        act_aug = torch.empty((rows, hd + 8), **bf)
+        gpre = torch.empty((rows, hd), **bf)
+        stats = torch.empty((2, rows), dtype=torch.float32, device=dev)
+        _lib.call(lib.vmasr_mlp_bwd, x2, gy2, g32, be32, float(eps), w1b, w1t, b1f, w2t, sc, rps, dxn, xn_aug, gys, act_aug, gpre,
+                  stats[0], stats[1], rows, d, _lib.torch_dtype_code(x2.dtype))
+        # dx = gy + LayerNorm'(dxn); dgamma, dbeta  (one launch: csrc/ln.hip with the residual gradient folded in)
+        dx = torch.empty_like(x2)
+        dg_ = torch.empty(d, dtype=torch.float32, device=dev)      # separate tensors: autograd adopts each as a .grad
+        db_ = torch.empty(d, dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.vmasr_layer_norm_bwd_workspace(rows, d) // 4, dtype=torch.float32, device=dev)
+        later = (gdt == torch.float32 and bedt == torch.float32 and ctx.fresh() and _ln.defer_reduction(ws, dg_, db_, rows, d, *ctx.params))
+        _lib.call(lib.vmasr_layer_norm_bwd_res, x2, dxn, g32, stats[0], stats[1], gy2, dx, dg_ if not later else None,
+                  db_ if not later else None, ws, rows, d, _lib.torch_dtype_code(x2.dtype), _lib.BF16)
         # [dW1 | db1 | 0] = gpre^T xn_aug,  [dW2 | db2 | 0] = gys^T act_aug  (fp32 accumulation, split over the rows when few tiles);
         # the sum over the slabs and the split into contiguous dW / db: one launch for ALL queued GEMMs of the pass (wgrad.py)
         fresh_w = _ln.fresh(*ctx.wparams)

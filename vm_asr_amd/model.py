@@ -69,12 +69,10 @@ class _Im2ColRowsFn(torch.autograd.Function):
         B, C, H, W = x.shape
         Ho, Wo = (H + 2 * p[0] - k[0]) // s[0] + 1, (W + 2 * p[1] - k[1]) // s[1] + 1
         dev = x.device
-        with torch.cuda.device(dev):
-            cols = torch.empty((B * Ho * Wo, C * k[0] * k[1]), dtype=dtype, device=dev)
-            st = (ctypes.c_int64 * 4)(*x.stride())
-            _lib.check(_lib.lib().vmasr_im2col2d_rows(x.data_ptr(), cols.data_ptr(), B, C, H, W, k[0], k[1], s[0], s[1], p[0], p[1], st,
-                                                      _lib.torch_dtype_code(x.dtype), _lib.torch_dtype_code(dtype), _lib.current_stream(dev)),
-                       "im2col2d_rows")
+        cols = torch.empty((B * Ho * Wo, C * k[0] * k[1]), dtype=dtype, device=dev)
+        st = (ctypes.c_int64 * 4)(*x.stride())
+        _lib.call(_lib.lib().vmasr_im2col2d_rows, x, cols, B, C, H, W, k[0], k[1], s[0], s[1], p[0], p[1], st, _lib.torch_dtype_code(x.dtype),
+                  _lib.torch_dtype_code(dtype))
         ctx.geom = (tuple(x.shape), tuple(x.stride()), x.dtype, k, s, p)
         return cols
 
@@ -86,12 +84,10 @@ class _Im2ColRowsFn(torch.autograd.Function):
         B, C, H, W = shape
         g = g.contiguous()
         dev = g.device
-        with torch.cuda.device(dev):
-            dx = torch.empty_strided(shape, strides, dtype=xdt, device=dev)
-            st = (ctypes.c_int64 * 4)(*strides)
-            _lib.check(_lib.lib().vmasr_col2im2d_rows(g.data_ptr(), dx.data_ptr(), B, C, H, W, k[0], k[1], s[0], s[1], p[0], p[1], st,
-                                                      _lib.torch_dtype_code(g.dtype), _lib.torch_dtype_code(xdt), _lib.current_stream(dev)),
-                       "col2im2d_rows")
+        dx = torch.empty_strided(shape, strides, dtype=xdt, device=dev)
+        st = (ctypes.c_int64 * 4)(*strides)
+        _lib.call(_lib.lib().vmasr_col2im2d_rows, g, dx, B, C, H, W, k[0], k[1], s[0], s[1], p[0], p[1], st, _lib.torch_dtype_code(g.dtype),
+                  _lib.torch_dtype_code(xdt))
         return dx, None, None, None, None
 
 

@@ -20,11 +20,9 @@ def need(*ts):
 
 
 def _call(fn, *args):
-    """fn(*args, stream) on the first tensor's device and current stream; tensors (contiguous, on the GPU) go in as pointers; non-zero raises."""
-    ts = [a for a in args if torch.is_tensor(a)]
-    need(*ts)
-    with torch.cuda.device(ts[0].device):
-        _lib.check(fn(*[_p(a) if torch.is_tensor(a) else a for a in args], _lib.current_stream(ts[0].device)), fn.__name__[len("vmasr_"):])
+    """_lib.call for tensors that must also be contiguous."""
+    need(*[a for a in args if torch.is_tensor(a)])
+    _lib.call(fn, *args)
 
 
 def _new(like, shape, dtype=None):
@@ -65,10 +63,8 @@ def im2col_kx1(xs, geom, C, k, stride, pad, rows=0):
     """-> cols (n, rows, k*C), (tap, channel) column order, zero rows below each slot's data (rows = 0, one slot: none); a launch per slot."""
     x0, (nseq0, H0), src = xs[0], geom[0], _ptrs(xs, len(geom))
     cols = _new(x0, (len(geom), rows or nseq0 * ((H0 + 2 * pad - k) // stride + 1), k * C))
-    with torch.cuda.device(x0.device):
-        for i, (nseq, H) in enumerate(geom):
-            _lib.check(_lib.lib().vmasr_im2col_kx1(src[i], cols[i].data_ptr(), nseq, H, C, k, stride, pad, rows, _lib.torch_dtype_code(x0.dtype),
-                                                   _lib.current_stream(x0.device)), "im2col_kx1")
+    for i, (nseq, H) in enumerate(geom):
+        _lib.call(_lib.lib().vmasr_im2col_kx1, src[i], cols[i], nseq, H, C, k, stride, pad, rows, _lib.torch_dtype_code(x0.dtype))
     return cols
 
 

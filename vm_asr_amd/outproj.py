@@ -11,7 +11,6 @@ the operand of the weight gradient) + one split-K GEMM; the stream's own gradien
 import torch
 
 from . import _lib, knobs
-from ._lib import ptr as _p
 from .wgrad import weight_grad_finished
 from . import layernorm as _ln
 from .linear import bf16_shadow, bf16_shadow_t
@@ -46,10 +45,8 @@ class _OutProjFn(torch.autograd.Function):
         wb = bf16_shadow(w).contiguous()
         rps = rows // scale.numel() if scale is not None else 0
         sc = None if scale is None else scale.detach().float().contiguous().view(-1)
-        with torch.cuda.device(x.device):
-            y = torch.empty_like(x2)
-            _lib.check(_lib.lib().vmasr_outproj_fwd(_p(g2), _p(wb), _p(x2), _p(sc), rps, _p(y), rows, d, _lib.torch_dtype_code(x2.dtype),
-                                                    _lib.current_stream(x.device)), "outproj_fwd")
+        y = torch.empty_like(x2)
+        _lib.call(_lib.lib().vmasr_outproj_fwd, g2, wb, x2, sc, rps, y, rows, d, _lib.torch_dtype_code(x2.dtype))
         ctx.save_for_backward(g2, wb, sc)
         ctx.wt = bf16_shadow_t(w, wb)
         ctx.meta = (g.shape, x.shape, x2.dtype, rps, w.dtype)
@@ -70,12 +67,10 @@ class _OutProjFn(torch.autograd.Function):
         if not gy2.is_contiguous():
             gy2 = gy2.contiguous()
         dev = g2.device
-        with torch.cuda.device(dev):
-            wt = ctx.wt if ctx.wt is not None else wb.t().contiguous()      # (2d, d)
-            dg = torch.empty((rows, di), dtype=torch.bfloat16, device=dev)
-            gys = torch.empty((rows, d), dtype=torch.bfloat16, device=dev)
-            _lib.check(_lib.lib().vmasr_outproj_bwd(_p(gy2), _p(wt), _p(sc), rps, _p(dg), _p(gys), rows, d, _lib.torch_dtype_code(gy2.dtype),
-                                                    _lib.current_stream(dev)), "outproj_bwd")
+        wt = ctx.wt if ctx.wt is not None else wb.t().contiguous()      # (2d, d)
+        dg = torch.empty((rows, di), dtype=torch.bfloat16, device=dev)
+        gys = torch.empty((rows, d), dtype=torch.bfloat16, device=dev)
+        _lib.call(_lib.lib().vmasr_outproj_bwd, gy2, wt, sc, rps, dg, gys, rows, d, _lib.torch_dtype_code(gy2.dtype))
         dw = None
         if ctx.needs_input_grad[1]:                                          # (d, 2d) fp32; finished with the pass' other weight gradients
             dw, _ = weight_grad_finished(gys, g2, di, ctx.wparam, None, _ln.fresh(ctx.wparam))

@@ -83,14 +83,13 @@ def fwd(u, delta, A, B, C, D=None, delta_bias=None, delta_softplus=False, nrows=
     lib = _lib.lib()
     chunk = lib.vmasr_sscan_chunk()
     n_chunks = (seqlen + chunk - 1) // chunk
-    with torch.cuda.device(u.device):
-        out = torch.empty_like(delta)
-        if out.stride(-1) != 1:
-            out = torch.empty(delta.shape, dtype=delta.dtype, device=delta.device)
-        x = torch.empty((batch, dim, n_chunks, dstate * 2), dtype=torch.float32, device=u.device)
-        p = _lib.SScanParams()
-        _fill(p, u, delta, A, B, C, D, delta_bias, out, x, delta_softplus, n_chunks)
-        _lib.check(lib.vmasr_sscan_fwd(ctypes.byref(p), _lib.current_stream(u.device)), "selective_scan_fwd")
+    out = torch.empty_like(delta)
+    if out.stride(-1) != 1:
+        out = torch.empty(delta.shape, dtype=delta.dtype, device=delta.device)
+    x = torch.empty((batch, dim, n_chunks, dstate * 2), dtype=torch.float32, device=u.device)
+    p = _lib.SScanParams()
+    _fill(p, u, delta, A, B, C, D, delta_bias, out, x, delta_softplus, n_chunks)
+    _lib.call(lib.vmasr_sscan_fwd, p, device=u.device)
     return [out, x]
 
 
@@ -108,29 +107,27 @@ def bwd(u, delta, A, B, C, D, delta_bias, dout, x, delta_softplus, nrows=1):
     if x is not None:
         _chk(x.dtype == torch.float32 and x.is_cuda and x.is_contiguous(), "x must be contiguous float32")
         _chk(tuple(x.shape) == (batch, dim, n_chunks, 2 * dstate), "x must have shape (batch, dim, n_chunks, 2*dstate)")
-    with torch.cuda.device(u.device):
-        du = torch.empty_like(u)
-        ddelta = torch.empty_like(delta)
-        if du.stride(-1) != 1:
-            du = torch.empty(u.shape, dtype=u.dtype, device=u.device)
-        if ddelta.stride(-1) != 1:
-            ddelta = torch.empty(u.shape, dtype=u.dtype, device=u.device)
-        f32 = dict(dtype=torch.float32, device=u.device)
-        dB, dC, dA, dD, ddelta_bias = _lib.zeros_f32(u.device, B.shape, C.shape, A.shape,
-                                                     (dim,) if D is not None else None,
-                                                     (dim,) if delta_bias is not None else None)
-        q = _lib.SScanBwdParams()
-        _fill(q.f, u, delta, A, B, C, D, delta_bias, None, x, delta_softplus, n_chunks)
-        q.dout_batch_stride, q.dout_d_stride = dout.stride(0), dout.stride(1)
-        q.du_batch_stride, q.du_d_stride = du.stride(0), du.stride(1)
-        q.ddelta_batch_stride, q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
-        q.dA_d_stride, q.dA_dstate_stride = dA.stride(0), dA.stride(1)
-        q.dout_ptr, q.du_ptr, q.ddelta_ptr = _ptr(dout), _ptr(du), _ptr(ddelta)
-        q.dA_ptr, q.dB_ptr, q.dC_ptr, q.dD_ptr, q.ddelta_bias_ptr = _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(ddelta_bias)
-        ws_bytes = lib.vmasr_sscan_bwd_workspace(ctypes.byref(q))
-        ws = torch.empty(max(ws_bytes, 4) // 4, **f32) if ws_bytes else None
-        q.ws_ptr, q.ws_bytes = _ptr(ws), ws_bytes
-        _lib.check(lib.vmasr_sscan_bwd(ctypes.byref(q), _lib.current_stream(u.device)), "selective_scan_bwd")
+    du = torch.empty_like(u)
+    ddelta = torch.empty_like(delta)
+    if du.stride(-1) != 1:
+        du = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    if ddelta.stride(-1) != 1:
+        ddelta = torch.empty(u.shape, dtype=u.dtype, device=u.device)
+    f32 = dict(dtype=torch.float32, device=u.device)
+    dB, dC, dA, dD, ddelta_bias = _lib.zeros_f32(u.device, B.shape, C.shape, A.shape, (dim,) if D is not None else None,
+                                                 (dim,) if delta_bias is not None else None)
+    q = _lib.SScanBwdParams()
+    _fill(q.f, u, delta, A, B, C, D, delta_bias, None, x, delta_softplus, n_chunks)
+    q.dout_batch_stride, q.dout_d_stride = dout.stride(0), dout.stride(1)
+    q.du_batch_stride, q.du_d_stride = du.stride(0), du.stride(1)
+    q.ddelta_batch_stride, q.ddelta_d_stride = ddelta.stride(0), ddelta.stride(1)
+    q.dA_d_stride, q.dA_dstate_stride = dA.stride(0), dA.stride(1)
+    q.dout_ptr, q.du_ptr, q.ddelta_ptr = _ptr(dout), _ptr(du), _ptr(ddelta)
+    q.dA_ptr, q.dB_ptr, q.dC_ptr, q.dD_ptr, q.ddelta_bias_ptr = _ptr(dA), _ptr(dB), _ptr(dC), _ptr(dD), _ptr(ddelta_bias)
+    ws_bytes = lib.vmasr_sscan_bwd_workspace(ctypes.byref(q))
+    ws = torch.empty(max(ws_bytes, 4) // 4, **f32) if ws_bytes else None
+    q.ws_ptr, q.ws_bytes = _ptr(ws), ws_bytes
+    _lib.call(lib.vmasr_sscan_bwd, q, device=u.device)
     # reference casts dB/dC back to the input dtype (cus/selective_scan.cpp:347)
     return [du, ddelta, dA, dB.to(B.dtype), dC.to(C.dtype), dD, ddelta_bias]
 

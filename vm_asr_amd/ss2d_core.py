@@ -7,8 +7,6 @@ i.e. lines 1472-1497 of SS2D.forward_corev2 (model/vmamba.py) for d_state 1, dt_
 high-resolution stages of every shipped config — with cross-scan, x_proj, dt_proj, the four scans and cross-merge
 fused around the scan (see the header of ss2d.hip).  Differentiable (one fused backward); no CPU fallback.
 """
-import ctypes
-
 import torch
 
 from . import _lib, knobs
@@ -37,16 +35,15 @@ class _SS2DCoreFn(torch.autograd.Function):
         wx, wdt, b32 = _f32c(Wx, (4, 3, D)), _f32c(Wdt, (4, D)), _f32c(dtb, (4, D))
         al, ds = _f32c(A_logs, (4 * D,)), _f32c(Ds, (4 * D,))
         f32 = dict(dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            xT = torch.empty_like(x)
-            state = torch.empty((B, 4 * D, nt, 2), **f32)
-            scratch = torch.empty((2, B, D, L), **f32)
-            y = None if pairs else torch.empty((B, D, L), **f32)
-            p = _lib.SS2DParams()
-            p.B, p.D, p.H, p.W, p.dtype, p.flags = B, D, H, W, _lib.torch_dtype_code(x.dtype), (1 if pairs else 0)
-            p.x, p.xT, p.Wx, p.Wdt, p.dtb, p.Alog, p.Ds = _p(x), _p(xT), _p(wx), _p(wdt), _p(b32), _p(al), _p(ds)
-            p.state, p.out02, p.out13, p.y = _p(state), _p(scratch[0]), _p(scratch[1]), _p(y)
-            _lib.check(_lib.lib().vmasr_ss2d_fwd(ctypes.byref(p), _lib.current_stream(x.device)), "ss2d_fwd")
+        xT = torch.empty_like(x)
+        state = torch.empty((B, 4 * D, nt, 2), **f32)
+        scratch = torch.empty((2, B, D, L), **f32)
+        y = None if pairs else torch.empty((B, D, L), **f32)
+        p = _lib.SS2DParams()
+        p.B, p.D, p.H, p.W, p.dtype, p.flags = B, D, H, W, _lib.torch_dtype_code(x.dtype), (1 if pairs else 0)
+        p.x, p.xT, p.Wx, p.Wdt, p.dtb, p.Alog, p.Ds = _p(x), _p(xT), _p(wx), _p(wdt), _p(b32), _p(al), _p(ds)
+        p.state, p.out02, p.out13, p.y = _p(state), _p(scratch[0]), _p(scratch[1]), _p(y)
+        _lib.call(_lib.lib().vmasr_ss2d_fwd, p, device=x.device)
         ctx.save_for_backward(x, xT, state, wx, wdt, b32, al, ds)
         ctx.meta = (Wx.dtype, Wdt.dtype, Wdt.shape, dtb.dtype, dtb.shape, A_logs.dtype, A_logs.shape, Ds.dtype)
         ctx.pairs = pairs
@@ -64,20 +61,19 @@ class _SS2DCoreFn(torch.autograd.Function):
             dyT = dyT.float().contiguous()
         f32 = dict(dtype=torch.float32, device=x.device)
         lib = _lib.lib()
-        with torch.cuda.device(x.device):
-            scratch = torch.empty((3, B, D, L), **f32)            # dyT (unless given), dx02, dx13
-            adj = torch.empty((B, 4 * D, nt, 2), **f32)
-            part = torch.empty(lib.vmasr_ss2d_part_floats(B, D, H, W), **f32)
-            dx = torch.empty_like(x)
-            grads = torch.empty(4 * 3 * D + 4 * 4 * D, **f32)
-            dWx, dWdt, ddtb, dAl, dDs = torch.split(grads, [12 * D, 4 * D, 4 * D, 4 * D, 4 * D])
-            p = _lib.SS2DParams()
-            p.B, p.D, p.H, p.W, p.dtype, p.flags = B, D, H, W, _lib.torch_dtype_code(x.dtype), (1 if ctx.pairs else 0)
-            p.x, p.xT, p.Wx, p.Wdt, p.dtb, p.Alog, p.Ds = _p(x), _p(xT), _p(wx), _p(wdt), _p(b32), _p(al), _p(ds)
-            p.state, p.out02, p.out13 = _p(state), _p(scratch[1]), _p(scratch[2])
-            p.dy, p.dyT, p.adj, p.part, p.dx = _p(dy), _p(dyT if ctx.pairs else scratch[0]), _p(adj), _p(part), _p(dx)
-            p.dWx, p.dWdt, p.ddtb, p.dAlog, p.dDs = _p(dWx), _p(dWdt), _p(ddtb), _p(dAl), _p(dDs)
-            _lib.check(lib.vmasr_ss2d_bwd(ctypes.byref(p), _lib.current_stream(x.device)), "ss2d_bwd")
+        scratch = torch.empty((3, B, D, L), **f32)            # dyT (unless given), dx02, dx13
+        adj = torch.empty((B, 4 * D, nt, 2), **f32)
+        part = torch.empty(lib.vmasr_ss2d_part_floats(B, D, H, W), **f32)
+        dx = torch.empty_like(x)
+        grads = torch.empty(4 * 3 * D + 4 * 4 * D, **f32)
+        dWx, dWdt, ddtb, dAl, dDs = torch.split(grads, [12 * D, 4 * D, 4 * D, 4 * D, 4 * D])
+        p = _lib.SS2DParams()
+        p.B, p.D, p.H, p.W, p.dtype, p.flags = B, D, H, W, _lib.torch_dtype_code(x.dtype), (1 if ctx.pairs else 0)
+        p.x, p.xT, p.Wx, p.Wdt, p.dtb, p.Alog, p.Ds = _p(x), _p(xT), _p(wx), _p(wdt), _p(b32), _p(al), _p(ds)
+        p.state, p.out02, p.out13 = _p(state), _p(scratch[1]), _p(scratch[2])
+        p.dy, p.dyT, p.adj, p.part, p.dx = _p(dy), _p(dyT if ctx.pairs else scratch[0]), _p(adj), _p(part), _p(dx)
+        p.dWx, p.dWdt, p.ddtb, p.dAlog, p.dDs = _p(dWx), _p(dWdt), _p(ddtb), _p(dAl), _p(dDs)
+        _lib.call(lib.vmasr_ss2d_bwd, p, device=x.device)
         return (dx, dWx.view(4, 3, D).to(wxdt), dWdt.view(wdtshape).to(wdtdt), ddtb.view(dtbshape).to(dtbdt),
                 dAl.view(alshape).to(aldt), dDs.to(dsdt), None)
 

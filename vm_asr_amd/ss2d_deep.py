@@ -6,8 +6,6 @@ dt_rank 2 / 4 / 8, d_inner 64..512, H*W <= 4096: the 64x64, 32x32 and 16x16 stag
 which vm_asr_amd/ss2d_core.py (d_inner <= 32, dt_rank 1) does not take.  Forward = 2 launches, backward = 3 launches + one small
 GEMM (dW_x) and one sum (the per-wave parameter sums) — where the unfused chain ran 4 + 6 launches and their ATen glue.
 """
-import ctypes
-
 import torch
 
 from . import _lib, knobs
@@ -43,12 +41,11 @@ class _SS2DDeepFn(torch.autograd.Function):
         wx = _f32c(Wx, (4, R + 2, D))           # as stored (no copy for an fp32 parameter): the kernels index (k, c, d) directly
         wdt, b32 = _f32c(Wdt, (4, D, R)), _f32c(dtb, (4, D))
         al, ds = _f32c(A_logs, (4 * D,)), _f32c(Ds, (4 * D,))
-        with torch.cuda.device(x.device):
-            xdbl = torch.empty((B, 4, R + 2, L), dtype=torch.float32, device=x.device)
-            y = torch.empty((B, D, L), dtype=torch.float32, device=x.device)
-            p = _params(x, R, wx, wdt, b32, al, ds, xdbl)
-            p.y = _p(y)
-            _lib.check(_lib.lib().vmasr_ss2d_deep_fwd(ctypes.byref(p), _lib.current_stream(x.device)), "ss2d_deep_fwd")
+        xdbl = torch.empty((B, 4, R + 2, L), dtype=torch.float32, device=x.device)
+        y = torch.empty((B, D, L), dtype=torch.float32, device=x.device)
+        p = _params(x, R, wx, wdt, b32, al, ds, xdbl)
+        p.y = _p(y)
+        _lib.call(_lib.lib().vmasr_ss2d_deep_fwd, p, device=x.device)
         ctx.save_for_backward(x, xdbl, wx, wdt, b32, al, ds)
         ctx.meta = (Wx.dtype, Wx.shape, Wdt.dtype, Wdt.shape, dtb.dtype, dtb.shape, A_logs.dtype, A_logs.shape, Ds.dtype)
         ps = (Wx, Wdt, dtb, A_logs, Ds)
@@ -69,27 +66,26 @@ class _SS2DDeepFn(torch.autograd.Function):
         dy = dy.float().contiguous()
         lib = _lib.lib()
         WR = int(lib.vmasr_ss2d_deep_waves_per_row(H, W))
-        with torch.cuda.device(x.device):
-            du = torch.empty((B, D, L), dtype=torch.float32, device=x.device)
-            terms = torch.empty((3, B, 4, D, L), dtype=x.dtype, device=x.device)
-            pg = torch.empty((B * WR, 4 * D, 20), dtype=torch.float32, device=x.device)      # per-(b, wave) slabs of (4 D, kPG)
-            dx = torch.empty_like(x)
-            gpos = torch.empty((B, 4 * C, L), dtype=x.dtype, device=x.device)
-            g32 = torch.empty((B, 4 * C, L), dtype=torch.float32, device=x.device)
-            p = _params(x, R, wx, wdt, b32, al, ds, xdbl)
-            p.dy, p.du, p.tp, p.tb, p.tc, p.pg, p.dx, p.gpos, p.g32 = (_p(dy), _p(du), _p(terms[0]), _p(terms[1]), _p(terms[2]), _p(pg), _p(dx),
-                                                                      _p(gpos), _p(g32))
-            _lib.check(lib.vmasr_ss2d_deep_bwd(ctypes.byref(p), _lib.current_stream(x.device)), "ss2d_deep_bwd")
-            # dW_x[kc][d] = sum_{b,p} gpos[b][kc][p] x[b][d][p]: (B, 4C, L) @ (B, L, D), fp32 accumulation, summed over the batch
-            px = _mm_acc(gpos, x.view(B, D, L).transpose(1, 2), torch.float32)          # (B, 4C, D): summed over the batch by the finish
-            dWx = torch.empty((4 * C, D), dtype=torch.float32, device=x.device)
-            Wx_ = ctx.params[0]
-            finish_slabs(px, D, (dWx,), (Wx_,), Wx_.grad is None and Wx_.dtype == torch.float32 and _ln.used_once(Wx_))
-            # the per-(b, wave) parameter sums -> dW_dt (4, D, R), d dt_bias (4, D), dA_log (4 D), dD (4 D): contiguous tensors,
-            # finished together with the pass' other parameter gradients in one launch (wgrad.py)
-            dWdt = torch.empty((4 * D, R), dtype=torch.float32, device=x.device)
-            ddtb, dal, dds = (torch.empty(4 * D, dtype=torch.float32, device=x.device) for _ in range(3))
-            finish_slabs(pg, R, (dWdt, ddtb, dal, dds), ctx.params[1:], ctx.fresh())
+        du = torch.empty((B, D, L), dtype=torch.float32, device=x.device)
+        terms = torch.empty((3, B, 4, D, L), dtype=x.dtype, device=x.device)
+        pg = torch.empty((B * WR, 4 * D, 20), dtype=torch.float32, device=x.device)      # per-(b, wave) slabs of (4 D, kPG)
+        dx = torch.empty_like(x)
+        gpos = torch.empty((B, 4 * C, L), dtype=x.dtype, device=x.device)
+        g32 = torch.empty((B, 4 * C, L), dtype=torch.float32, device=x.device)
+        p = _params(x, R, wx, wdt, b32, al, ds, xdbl)
+        p.dy, p.du, p.tp, p.tb, p.tc, p.pg, p.dx, p.gpos, p.g32 = (_p(dy), _p(du), _p(terms[0]), _p(terms[1]), _p(terms[2]), _p(pg), _p(dx),
+                                                                  _p(gpos), _p(g32))
+        _lib.call(lib.vmasr_ss2d_deep_bwd, p, device=x.device)
+        # dW_x[kc][d] = sum_{b,p} gpos[b][kc][p] x[b][d][p]: (B, 4C, L) @ (B, L, D), fp32 accumulation, summed over the batch
+        px = _mm_acc(gpos, x.view(B, D, L).transpose(1, 2), torch.float32)          # (B, 4C, D): summed over the batch by the finish
+        dWx = torch.empty((4 * C, D), dtype=torch.float32, device=x.device)
+        Wx_ = ctx.params[0]
+        finish_slabs(px, D, (dWx,), (Wx_,), Wx_.grad is None and Wx_.dtype == torch.float32 and _ln.used_once(Wx_))
+        # the per-(b, wave) parameter sums -> dW_dt (4, D, R), d dt_bias (4, D), dA_log (4 D), dD (4 D): contiguous tensors,
+        # finished together with the pass' other parameter gradients in one launch (wgrad.py)
+        dWdt = torch.empty((4 * D, R), dtype=torch.float32, device=x.device)
+        ddtb, dal, dds = (torch.empty(4 * D, dtype=torch.float32, device=x.device) for _ in range(3))
+        finish_slabs(pg, R, (dWdt, ddtb, dal, dds), ctx.params[1:], ctx.fresh())
         return (dx, dWx.view(wxshape).to(wxdt), dWdt.view(wdtshape).to(wdtdt), ddtb.view(dtbshape).to(dtbdt),
                 dal.view(alshape).to(aldt), dds.to(dsdt))
 

@@ -10,7 +10,6 @@ Both differentiable (one launch per direction); no CPU fallback.
 import torch
 
 from . import _lib, knobs
-from ._lib import ptr as _p
 from . import layernorm as _ln
 
 __all__ = ["ss2d_pre", "ln_gate", "ln_gate_pairs", "pairs_supported", "supported"]
@@ -28,11 +27,9 @@ class _PreFn(torch.autograd.Function):
         B, H, W, D2 = xz.shape
         D, L = D2 // 2, H * W
         xz = xz.contiguous()
-        with torch.cuda.device(xz.device):
-            xT = torch.empty((B, D, H, W), dtype=xz.dtype, device=xz.device)
-            sz = torch.empty((B, H, W, D), dtype=xz.dtype, device=xz.device)
-            _lib.check(_lib.lib().vmasr_ss2d_pre_fwd(_p(xz), _p(xT), _p(sz), B, D, L, _lib.torch_dtype_code(xz.dtype),
-                                                     _lib.current_stream(xz.device)), "ss2d_pre_fwd")
+        xT = torch.empty((B, D, H, W), dtype=xz.dtype, device=xz.device)
+        sz = torch.empty((B, H, W, D), dtype=xz.dtype, device=xz.device)
+        _lib.call(_lib.lib().vmasr_ss2d_pre_fwd, xz, xT, sz, B, D, L, _lib.torch_dtype_code(xz.dtype))
         ctx.save_for_backward(xz)
         return xT, sz
 
@@ -44,10 +41,8 @@ class _PreFn(torch.autograd.Function):
         dt = xz.dtype
         dxT = (torch.zeros((B, D, H, W), dtype=dt, device=xz.device) if dxT is None else dxT.to(dt)).contiguous()
         dsz = (torch.zeros((B, H, W, D), dtype=dt, device=xz.device) if dsz is None else dsz.to(dt)).contiguous()
-        with torch.cuda.device(xz.device):
-            dxz = torch.empty_like(xz)
-            _lib.check(_lib.lib().vmasr_ss2d_pre_bwd(_p(xz), _p(dxT), _p(dsz), _p(dxz), B, D, L, _lib.torch_dtype_code(dt),
-                                                     _lib.current_stream(xz.device)), "ss2d_pre_bwd")
+        dxz = torch.empty_like(xz)
+        _lib.call(_lib.lib().vmasr_ss2d_pre_bwd, xz, dxT, dsz, dxz, B, D, L, _lib.torch_dtype_code(dt))
         return dxz
 
 
@@ -59,12 +54,10 @@ class _LNGateFn(torch.autograd.Function):
         y = y.float().contiguous()
         sz = sz.contiguous()
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        with torch.cuda.device(sz.device):
-            out = torch.empty_like(sz)
-            stats = torch.empty((2, B, L), dtype=torch.float32, device=sz.device)
-            _lib.check(_lib.lib().vmasr_ln_gate_fwd(_p(y), _p(sz), _p(g32), _p(b32), _p(out), _p(stats[0]), _p(stats[1]), B, D, L,
-                                                    float(eps), _lib.torch_dtype_code(sz.dtype), _lib.current_stream(sz.device)),
-                       "ln_gate_fwd")
+        out = torch.empty_like(sz)
+        stats = torch.empty((2, B, L), dtype=torch.float32, device=sz.device)
+        _lib.call(_lib.lib().vmasr_ln_gate_fwd, y, sz, g32, b32, out, stats[0], stats[1], B, D, L, float(eps),
+                  _lib.torch_dtype_code(sz.dtype))
         ctx.save_for_backward(y, sz, g32, b32, stats)
         ctx.meta = (gamma.dtype, beta.dtype)
         if any(ctx.needs_input_grad[2:4]):
@@ -80,25 +73,22 @@ class _LNGateFn(torch.autograd.Function):
         L = H * W
         dout = dout.to(sz.dtype).contiguous()
         lib, code = _lib.lib(), _lib.torch_dtype_code(sz.dtype)
-        with torch.cuda.device(sz.device):
-            dy = torch.empty_like(y)
-            dsz = torch.empty_like(sz)
-            nws = int(lib.vmasr_ln_gate_bwd_workspace(B, D, L, code))
-            if nws:
-                # d_inner >= 64: per-workgroup partials of dgamma / dbeta, reduced at once or — in the trainer's flat-gradient
-                # mode — by the one reduce launch at the end of the backward pass (layernorm.defer_reduction)
-                ws = torch.empty(nws, dtype=torch.float32, device=sz.device)
-                dg = torch.empty(D, dtype=torch.float32, device=sz.device)
-                db = torch.empty(D, dtype=torch.float32, device=sz.device)
-                later = (_ln.DEFER_REDUCE and ctx.meta == (torch.float32, torch.float32) and ctx.fresh()
-                         and _ln.defer_reduction(ws, dg, db, None, D, *ctx.params, nblk=nws // (2 * D)))
-                _lib.check(lib.vmasr_ln_gate_bwd_ws(_p(y), _p(sz), _p(dout), _p(g32), _p(b32), _p(stats[0]), _p(stats[1]), _p(dy), _p(dsz),
-                                                    None if later else _p(dg), None if later else _p(db), _p(ws), B, D, L, code,
-                                                    _lib.current_stream(sz.device)), "ln_gate_bwd_ws")
-                return dy, dsz, dg.to(ctx.meta[0]), db.to(ctx.meta[1]), None
-            dgb, = _lib.zeros_f32(sz.device, (2, D))
-            _lib.check(lib.vmasr_ln_gate_bwd(_p(y), _p(sz), _p(dout), _p(g32), _p(b32), _p(stats[0]), _p(stats[1]), _p(dy), _p(dsz),
-                                             _p(dgb[0]), _p(dgb[1]), B, D, L, code, _lib.current_stream(sz.device)), "ln_gate_bwd")
+        dy = torch.empty_like(y)
+        dsz = torch.empty_like(sz)
+        nws = int(lib.vmasr_ln_gate_bwd_workspace(B, D, L, code))
+        if nws:
+            # d_inner >= 64: per-workgroup partials of dgamma / dbeta, reduced at once or — in the trainer's flat-gradient
+            # mode — by the one reduce launch at the end of the backward pass (layernorm.defer_reduction)
+            ws = torch.empty(nws, dtype=torch.float32, device=sz.device)
+            dg = torch.empty(D, dtype=torch.float32, device=sz.device)
+            db = torch.empty(D, dtype=torch.float32, device=sz.device)
+            later = (_ln.DEFER_REDUCE and ctx.meta == (torch.float32, torch.float32) and ctx.fresh()
+                     and _ln.defer_reduction(ws, dg, db, None, D, *ctx.params, nblk=nws // (2 * D)))
+            _lib.call(lib.vmasr_ln_gate_bwd_ws, y, sz, dout, g32, b32, stats[0], stats[1], dy, dsz, dg if not later else None,
+                      db if not later else None, ws, B, D, L, code)
+            return dy, dsz, dg.to(ctx.meta[0]), db.to(ctx.meta[1]), None
+        dgb, = _lib.zeros_f32(sz.device, (2, D))
+        _lib.call(lib.vmasr_ln_gate_bwd, y, sz, dout, g32, b32, stats[0], stats[1], dy, dsz, dgb[0], dgb[1], B, D, L, code)
         return dy, dsz, dgb[0].to(ctx.meta[0]), dgb[1].to(ctx.meta[1]), None
 
 
@@ -111,12 +101,10 @@ class _LNGatePairsFn(torch.autograd.Function):
         y02, y13 = y02.float().contiguous(), y13.float().contiguous()
         sz = sz.contiguous()
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        with torch.cuda.device(sz.device):
-            out = torch.empty_like(sz)
-            stats = torch.empty((2, B, H * W), dtype=torch.float32, device=sz.device)
-            _lib.check(_lib.lib().vmasr_ln_gate_pair_fwd(_p(y02), _p(y13), _p(sz), _p(g32), _p(b32), _p(out), _p(stats[0]), _p(stats[1]),
-                                                         B, D, H, W, float(eps), _lib.torch_dtype_code(sz.dtype),
-                                                         _lib.current_stream(sz.device)), "ln_gate_pair_fwd")
+        out = torch.empty_like(sz)
+        stats = torch.empty((2, B, H * W), dtype=torch.float32, device=sz.device)
+        _lib.call(_lib.lib().vmasr_ln_gate_pair_fwd, y02, y13, sz, g32, b32, out, stats[0], stats[1], B, D, H, W, float(eps),
+                  _lib.torch_dtype_code(sz.dtype))
         ctx.save_for_backward(y02, y13, sz, g32, b32, stats)
         ctx.meta = (gamma.dtype, beta.dtype)
         return out
@@ -126,13 +114,11 @@ class _LNGatePairsFn(torch.autograd.Function):
         y02, y13, sz, g32, b32, stats = ctx.saved_tensors
         B, H, W, D = sz.shape
         dout = dout.to(sz.dtype).contiguous()
-        with torch.cuda.device(sz.device):
-            dys = torch.empty((2,) + tuple(y02.shape), dtype=torch.float32, device=sz.device)
-            dsz = torch.empty_like(sz)
-            dgb, = _lib.zeros_f32(sz.device, (2, D))
-            _lib.check(_lib.lib().vmasr_ln_gate_pair_bwd(_p(y02), _p(y13), _p(sz), _p(dout), _p(g32), _p(b32), _p(stats[0]), _p(stats[1]),
-                                                         _p(dys[0]), _p(dys[1]), _p(dsz), _p(dgb[0]), _p(dgb[1]), B, D, H, W,
-                                                         _lib.torch_dtype_code(sz.dtype), _lib.current_stream(sz.device)), "ln_gate_pair_bwd")
+        dys = torch.empty((2,) + tuple(y02.shape), dtype=torch.float32, device=sz.device)
+        dsz = torch.empty_like(sz)
+        dgb, = _lib.zeros_f32(sz.device, (2, D))
+        _lib.call(_lib.lib().vmasr_ln_gate_pair_bwd, y02, y13, sz, dout, g32, b32, stats[0], stats[1], dys[0], dys[1], dsz, dgb[0], dgb[1],
+                  B, D, H, W, _lib.torch_dtype_code(sz.dtype))
         return dys[0], dys[1], dsz, dgb[0].to(ctx.meta[0]), dgb[1].to(ctx.meta[1]), None
 
 

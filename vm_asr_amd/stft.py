@@ -16,7 +16,6 @@ from typing import Tuple
 import torch
 
 from . import _lib
-from ._lib import ptr as _p
 
 __all__ = ["wav2spectro", "spectro2wav", "stft_complex", "stft_reim", "ISTFTFunction", "STFTReImFunction"]
 
@@ -27,11 +26,9 @@ def _stft(waveform, n_fft, hop, win, normalized, logmag):
     w = waveform.reshape(-1, length).float().contiguous()
     Bn = w.shape[0]
     F, M = n_fft // 2 + 1, 1 + length // hop
-    with torch.cuda.device(w.device):
-        o0 = torch.empty((Bn, F, M), dtype=torch.float32, device=w.device)
-        o1 = torch.empty_like(o0)
-        _lib.check(_lib.lib().vmasr_stft(_p(w), _p(o0), _p(o1), Bn, length, n_fft, hop, win, int(normalized),
-                                         int(logmag), _lib.current_stream(w.device)), "stft")
+    o0 = torch.empty((Bn, F, M), dtype=torch.float32, device=w.device)
+    o1 = torch.empty_like(o0)
+    _lib.call(_lib.lib().vmasr_stft, w, o0, o1, Bn, length, n_fft, hop, win, int(normalized), int(logmag))
     return o0.view(*other, F, M), o1.view(*other, F, M)
 
 
@@ -70,12 +67,10 @@ class STFTReImFunction(torch.autograd.Function):
         gre, gim = gre.reshape(-1, F, M).float().contiguous(), gim.reshape(-1, F, M).float().contiguous()
         Bn = gre.shape[0]
         lib = _lib.lib()
-        with torch.cuda.device(gre.device):
-            gw = torch.empty((Bn, T), dtype=torch.float32, device=gre.device)
-            wsb = lib.vmasr_stft_bwd_workspace(Bn, T, n_fft, hop)
-            ws = torch.empty(wsb // 4, dtype=torch.float32, device=gre.device)
-            _lib.check(lib.vmasr_stft_bwd(_p(gre), _p(gim), _p(gw), Bn, T, n_fft, hop, win, int(normalized), _p(ws), wsb,
-                                          _lib.current_stream(gre.device)), "stft_bwd")
+        gw = torch.empty((Bn, T), dtype=torch.float32, device=gre.device)
+        wsb = lib.vmasr_stft_bwd_workspace(Bn, T, n_fft, hop)
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=gre.device)
+        _lib.call(lib.vmasr_stft_bwd, gre, gim, gw, Bn, T, n_fft, hop, win, int(normalized), ws, wsb)
         return gw.view(shape), None, None, None, None
 
 
@@ -91,12 +86,10 @@ class ISTFTFunction(torch.autograd.Function):
         Bn, F, M = mag.shape
         mag, phase = mag.contiguous(), phase.contiguous()
         lib = _lib.lib()
-        with torch.cuda.device(mag.device):
-            wav = torch.empty((Bn, hop * (M - 1)), dtype=torch.float32, device=mag.device)
-            wsb = lib.vmasr_istft_workspace(Bn, F, M, hop)
-            ws = torch.empty(wsb // 4, dtype=torch.float32, device=mag.device)
-            _lib.check(lib.vmasr_istft(_p(mag), _p(phase), _p(wav), Bn, F, M, hop, win, _p(ws), wsb,
-                                       _lib.current_stream(mag.device)), "istft")
+        wav = torch.empty((Bn, hop * (M - 1)), dtype=torch.float32, device=mag.device)
+        wsb = lib.vmasr_istft_workspace(Bn, F, M, hop)
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=mag.device)
+        _lib.call(lib.vmasr_istft, mag, phase, wav, Bn, F, M, hop, win, ws, wsb)
         ctx.save_for_backward(mag, phase)
         ctx.cfg = (hop, win)
         return wav
@@ -108,10 +101,8 @@ class ISTFTFunction(torch.autograd.Function):
         hop, win = ctx.cfg
         Bn, F, M = mag.shape
         g = g.float().contiguous()
-        with torch.cuda.device(mag.device):
-            dmag, dphase = torch.empty_like(mag), torch.empty_like(phase)
-            _lib.check(_lib.lib().vmasr_istft_bwd(_p(mag), _p(phase), _p(g), _p(dmag), _p(dphase), Bn, F, M, hop,
-                                                  win, _lib.current_stream(mag.device)), "istft_bwd")
+        dmag, dphase = torch.empty_like(mag), torch.empty_like(phase)
+        _lib.call(_lib.lib().vmasr_istft_bwd, mag, phase, g, dmag, dphase, Bn, F, M, hop, win)
         return dmag, dphase, None, None
 
 

@@ -808,7 +808,7 @@ class Trainer(BaseTrainer):
         if not hasattr(self, "phase_marks"):
             self.phase_marks, self._phase_buf = {}, torch.zeros(64, dtype=torch.int64, device=self.device)
         slot = self.phase_marks.setdefault(name, len(self.phase_marks))
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)   # a chosen stream: by hand, not _lib.call
         _lib.check(_lib.lib().vmasr_mark_time(self._phase_buf.data_ptr() + 8 * slot, st.cuda_stream), "mark_time")
 
     def _side_stream(self):

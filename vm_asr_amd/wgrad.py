@@ -49,10 +49,8 @@ def _launch(items):
     e1s = np.array([it.get("e1_ptr", 0) for it in items], dtype=np.uint64)
     e2s = np.array([it.get("e2_ptr", 0) for it in items], dtype=np.uint64)
     Ss, Ns, Ks, lds = arr("S", np.int32), arr("N", np.int32), arr("K", np.int32), arr("ld", np.int32)
-    dev = items[0]["parts"].device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().vmasr_wgrad_finish_multi(parts.ctypes.data, dws.ctypes.data, dbs.ctypes.data, e1s.ctypes.data, e2s.ctypes.data, Ss.ctypes.data, Ns.ctypes.data,
-                                                       Ks.ctypes.data, lds.ctypes.data, n, _lib.current_stream(dev)), "wgrad_finish_multi")
+    _lib.call(_lib.lib().vmasr_wgrad_finish_multi, parts.ctypes.data, dws.ctypes.data, dbs.ctypes.data, e1s.ctypes.data, e2s.ctypes.data,
+              Ss.ctypes.data, Ns.ctypes.data, Ks.ctypes.data, lds.ctypes.data, n, device=items[0]["parts"].device)
 
 
 def _parts(gy2, x2):
@@ -75,9 +73,8 @@ def weight_grad_finished(gy2, x_aug, K, weight=None, bias=None, fresh=False):
     S, N, ld = parts.shape
     has_b = ld > K
     dev = parts.device
-    with torch.cuda.device(dev):
-        dw = torch.empty((N, K), dtype=torch.float32, device=dev)
-        db = torch.empty(N, dtype=torch.float32, device=dev) if has_b else None
+    dw = torch.empty((N, K), dtype=torch.float32, device=dev)
+    db = torch.empty(N, dtype=torch.float32, device=dev) if has_b else None
     ref = lambda t: (None, 0, None) if t is None else (t.untyped_storage(), t.data_ptr(), tuple(t.shape))   # noqa: E731
     item = dict(parts=parts, parts_ptr=parts.data_ptr(), dw_ptr=dw.data_ptr(), db_ptr=0 if db is None else db.data_ptr(), S=S, N=N, K=K,
                 ld=ld, wparam=weight, bparam=bias, dw_ref=ref(dw), db_ref=ref(db))

@@ -10,7 +10,6 @@ Equivalent to the two einsums + split + contiguous + float casts of SS2D.forward
 import torch
 
 from . import _lib
-from ._lib import ptr as _p
 
 __all__ = ["x_proj_dt", "supported"]
 
@@ -37,14 +36,12 @@ class _XProjFn(torch.autograd.Function):
         xs = xs.contiguous()
         wx32, wdt32 = Wx.detach().float().contiguous(), Wdt.detach().float().contiguous()
         f32 = dict(dtype=torch.float32, device=xs.device)
-        with torch.cuda.device(xs.device):
-            dts = torch.empty((B, K * D, L), **f32)
-            Bs = torch.empty((B, K, N, L), **f32)
-            Cs = torch.empty((B, K, N, L), **f32)
-            dtr = torch.empty((B, K, R, L), **f32)
-            fn = _lib.lib().vmasr_xproj_n_fwd if _general(N, R, D) else _lib.lib().vmasr_xproj_fwd
-            _lib.check(fn(_p(xs), _p(wx32), _p(wdt32), _p(dts), _p(Bs), _p(Cs), _p(dtr), B, K, D, N, R,
-                          L, _lib.torch_dtype_code(xs.dtype), _lib.current_stream(xs.device)), "xproj_fwd")
+        dts = torch.empty((B, K * D, L), **f32)
+        Bs = torch.empty((B, K, N, L), **f32)
+        Cs = torch.empty((B, K, N, L), **f32)
+        dtr = torch.empty((B, K, R, L), **f32)
+        fn = _lib.lib().vmasr_xproj_n_fwd if _general(N, R, D) else _lib.lib().vmasr_xproj_fwd
+        _lib.call(fn, xs, wx32, wdt32, dts, Bs, Cs, dtr, B, K, D, N, R, L, _lib.torch_dtype_code(xs.dtype))
         ctx.save_for_backward(xs, wx32, wdt32, dtr)
         ctx.meta = (N, Wx.dtype, Wdt.dtype)
         return dts, Bs, Cs
@@ -59,15 +56,12 @@ class _XProjFn(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=xs.device)
         z = lambda t, shape: torch.zeros(shape, **f32) if t is None else t.float().contiguous()  # noqa: E731
         ddts, dBs, dCs = z(ddts, (B, K * D, L)), z(dBs, (B, K, N, L)), z(dCs, (B, K, N, L))
-        with torch.cuda.device(xs.device):
-            dxs = torch.empty_like(xs)
-            dWx, dWdt = _lib.zeros_f32(xs.device, (K, C, D), (K, D, R))
-            gen = _general(N, R, D)
-            ws = torch.empty((B, K, R if gen else C, L), **f32)     # general N: only the low-rank dt rows' gradient is kept
-            fn = _lib.lib().vmasr_xproj_n_bwd if gen else _lib.lib().vmasr_xproj_bwd
-            _lib.check(fn(_p(xs), _p(wx32), _p(wdt32), _p(dtr), _p(ddts), _p(dBs), _p(dCs), None,
-                          _p(dxs), _p(dWx), _p(dWdt), _p(ws), B, K, D, N, R, L,
-                          _lib.torch_dtype_code(xs.dtype), _lib.current_stream(xs.device)), "xproj_bwd")
+        dxs = torch.empty_like(xs)
+        dWx, dWdt = _lib.zeros_f32(xs.device, (K, C, D), (K, D, R))
+        gen = _general(N, R, D)
+        ws = torch.empty((B, K, R if gen else C, L), **f32)     # general N: only the low-rank dt rows' gradient is kept
+        fn = _lib.lib().vmasr_xproj_n_bwd if gen else _lib.lib().vmasr_xproj_bwd
+        _lib.call(fn, xs, wx32, wdt32, dtr, ddts, dBs, dCs, None, dxs, dWx, dWdt, ws, B, K, D, N, R, L, _lib.torch_dtype_code(xs.dtype))
         return dxs, dWx.to(wxdt), dWdt.to(wdtdt), None
 
 
