@@ -184,6 +184,17 @@ size_t vmasr_metrics_workspace(int32_t B, int32_t T, int32_t n_fft, int32_t hop)
 int vmasr_metrics(const float *out, const float *tgt, const int64_t *hf, float *per_clip, double *acc, int32_t B, int32_t T,
                   int32_t n_fft, int32_t hop, void *ws, size_t ws_bytes, vmasr_stream_t stream);
 
+/* Polyphase FIR resampling of B rows, scipy.signal.resample_poly(x, up, down) with padtype "constant"
+ * (data_loader/data_loaders.py:340,472-478, trainer/inferencer.py:270; csrc/resample.hip): x (B,n_in) fp32 contiguous, h the
+ * 2*half_len+1 fp32 taps ALREADY multiplied by `up`, y (B,n_out) fp32:
+ *     y[b,m] = sum_q x[b,q] * h[half_len + m*down - q*up]        x zero outside [0,n_in), h index inside [0, 2*half_len]
+ * With h = up * firwin(2*half_len+1, 1/max(up,down), window=("kaiser", 5.0)) and half_len = 10*max(up,down) this is scipy's
+ * default filter (vm_asr_amd/resample.py:design).  VMASR_EINVAL, nothing launched: a null pointer; B, n_in, up or down <= 0;
+ * gcd(up,down) != 1; n_out != ceil(n_in*up/down); half_len < 0; B > 65535; sizes past the 64-bit index arithmetic.  Every
+ * accepted ratio is computed: one whose input window does not fit in LDS reads x from global memory. */
+int vmasr_resample_poly(const float *x, const float *h, float *y, int32_t B, int64_t n_in, int64_t n_out, int32_t up, int32_t down,
+                        int32_t half_len, vmasr_stream_t stream);
+
 /* Channel-last LayerNorm over the last dimension (F.layer_norm on (rows, C) with C <= 1024):
  * SS2D.out_norm, VSSBlock.norm/norm2, PatchMerging2D.norm, PatchExpanding.norm
  * (model/vmamba.py:767-769,1793,1817; model/model.py:70,105-108,620,631).
@@ -686,6 +697,7 @@ enum {
     VMASR_K_WGRAD_FINISH,       /* sum over split-K slabs + bias column split-off of many weight gradients, one launch (csrc/wgrad.hip) */
     VMASR_K_SKINNY_LINEAR,      /* y = x W^T + b for >= 4096 rows and <= 96 features each side (csrc/skinny.hip) */
     VMASR_K_METRICS,            /* SNR / LSD / LSD-HF / LSD-LF of a batch: packed out/tgt FFT per frame + finish (csrc/metrics.hip) */
+    VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };
 /* Deterministic-reduction switch (debug aid, off by default; the Python side turns it on for VMASR_DETERMINISTIC=1): the kernels whose

@@ -1,13 +1,17 @@
-"""Thin command line over vm_asr_amd with the reference's flags (main.py:28-318): train / --eval on the HIP path.
+"""Thin command line over vm_asr_amd with the reference's flags (main.py:28-318): train / --eval / --inference on the HIP path.
 
     python main.py --cfg configs/vm_asr_48k_MPD.yaml --synthetic 64                 # train (one process per GPU)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --cfg ... --synthetic 512
-    python main.py --cfg ... --eval --resume logs/.../ --tag 16000_48000 --synthetic 8
+    python main.py --cfg ... --eval --resume logs/.../ --tag 16000_48000 --synthetic 8 --degrade
+    python main.py --cfg ... --inference --input speech.wav --resume logs/.../ --tag 16000_48000     # or --input <directory>
 
-`--cfg` takes the reference's yaml files unchanged.  The VCTK pipeline (download, resampling, low-pass filters:
+`--cfg` takes the reference's yaml files unchanged.  The VCTK pipeline (download, flac decoding, dataset splits:
 data_loader/data_loaders.py) is out of scope: clips come from `--synthetic N` (trainer.SyntheticVCTK, the
 reference's batch contract) — a real dataset plugs in as any DataLoader yielding `(wave_in, wave_tgt, highcut, name,
-pad)`.  `--inference` (file I/O, wav decoding) is not built; `--throughput` runs bench.py's measurement.
+pad)`.  `--degrade` replaces each clip's input by the reference's degradation of its target, computed on the device
+(vm_asr_amd.resample.DegradeOnDevice: resampled down and up again; the rate is TAG's under --eval, a seeded draw from
+DATA.RANDOM_RESAMPLE per clip in training).  `--inference --input <wav file or directory>` enhances wav files
+(vm_asr_amd.inferencer) and writes `{stem}_enhanced.wav`; `--throughput` runs bench.py's measurement.
 """
 import argparse
 import os
@@ -42,6 +46,9 @@ def parse_option(argv=None):
     p.add_argument("--synthetic", type=int, default=64, help="number of synthetic VCTK-shaped clips per epoch")
     p.add_argument("--epochs", type=int, help="override TRAIN.EPOCHS")
     p.add_argument("--no-graphs", action="store_true", help="run the step eagerly instead of replaying HIP graphs")
+    p.add_argument("--degrade", action="store_true",
+                   help="make each clip's input from its target on the device: resampled down and up again (resample.DegradeOnDevice)")
+    p.add_argument("--segment-batch", type=int, default=1, help="--inference: segments of a long file per generator call")
     p.add_argument("--step-metrics", action="store_true",
                    help="metrics on every step / clip through the fused kernel (Trainer step_metrics, Tester fused_metrics)")
     args = p.parse_args(argv)
@@ -62,8 +69,8 @@ def main(args, config):
     from vm_asr_amd.trainer import (CosineWarmupScheduler, SyntheticVCTK, Trainer, _Logger, build_optimizer, default_metric_ftns,
                                     init_distributed)
     log = _Logger()
-    if config.INFERENCE_MODE:
-        raise SystemExit("--inference is not built (wav file I/O is out of scope, DESIGN.md §7); use --eval")
+    if config.INFERENCE_MODE and not args.input:
+        raise SystemExit("--inference needs --input <wav file or directory>")
     if config.THROUGHPUT_MODE:
         import subprocess
         raise SystemExit(subprocess.call([sys.executable, os.path.join(ROOT, "bench.py")]))   # child process, exit with its code
@@ -74,17 +81,31 @@ def main(args, config):
     torch.cuda.set_device(device)
     torch.manual_seed(config.SEED)
     models = vm_asr_amd.get_model(config)
+    if config.INFERENCE_MODE:
+        from vm_asr_amd.inferencer import Inferencer
+        inf = Inferencer({"generator": models["generator"]}, config, device, log, segment_batch=args.segment_batch)
+        if os.path.isdir(args.input):
+            print("\n".join(inf.infer_directory(args.input)))
+        else:
+            inf.infer_file(args.input)
+        return
     metrics = default_metric_ftns(config)
     sr_in = args.input_sr or (16000 if config.DATA.TARGET_SR == 48000 else 8000)
     if config.EVAL_MODE:
         from vm_asr_amd.tester import Tester
         ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 10_000)
         loader = torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False)
+        if args.degrade:
+            from vm_asr_amd.resample import DegradeOnDevice
+            loader = DegradeOnDevice(loader, config, device, sr_input=int(str(config.TAG).split("_")[0]))
         res = Tester({"generator": models["generator"]}, metrics, config, device, loader, log, fused_metrics=args.step_metrics).evaluate()
         print({k: round(v, 4) if isinstance(v, float) else v for k, v in res.items()})
         return
     ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 1000 * rank)
     loader = torch.utils.data.DataLoader(ds, batch_size=config.DATA.BATCH_SIZE, shuffle=False, drop_last=True)
+    if args.degrade:
+        from vm_asr_amd.resample import DegradeOnDevice
+        loader = DegradeOnDevice(loader, config, device, seed=config.SEED + 1000 * rank)
     gan = config.TRAIN.ADVERSARIAL.ENABLE
     graphs = not args.no_graphs and config.TRAIN.ACCUMULATION_STEPS == 1
     for m in models.values():

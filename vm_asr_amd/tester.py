@@ -22,7 +22,7 @@ import torch
 
 from .trainer import _Logger, unwrap
 
-__all__ = ["unfold_audio", "fold_audio", "BaseTester", "Tester"]
+__all__ = ["unfold_audio", "fold_audio", "frames_per_segment", "write_pcm16", "device_sync", "enhance", "BaseTester", "Tester"]
 
 
 def unfold_audio(audio, segment_length, overlap):
@@ -41,6 +41,46 @@ def fold_audio(segments, total_length, segment_length, overlap):
         out[:, :, i * step:i * step + segment_length] += segments[:, :, i]
         cnt[:, :, i * step:i * step + segment_length] += 1
     return out / cnt.clamp(min=1)
+
+
+def frames_per_segment(config, target_sr):
+    """Samples of one training segment at `target_sr` (trainer/tester.py:38-42, trainer/inferencer.py:35-39)."""
+    return int(int(config.DATA.SEGMENT * config.DATA.FLAC2WAV.SRC_SR) * target_sr / config.DATA.FLAC2WAV.SRC_SR)
+
+
+def write_pcm16(path, wave_1d, sample_rate):
+    """Mono 16-bit PCM wav of a 1-D float tensor in [-1, 1] (clamped; scaled by 32767, rounded)."""
+    pcm = (wave_1d.float().clamp(-1, 1) * 32767.0).round().to(torch.int16).cpu().numpy()
+    with wave.open(path, "wb") as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(pcm.tobytes())
+
+
+def device_sync(device):
+    """Wait for the device's queued work (the timed region of an evaluation or inference run starts and ends here)."""
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+
+
+def enhance(gen, wave_input, highcut, segment_length, overlap, segment_batch=1):
+    """gen over (B, C, T): one call when T fits a segment, else over overlapping segments cross-averaged back
+    (trainer/tester.py:92-130, trainer/inferencer.py:75-103).  Up to `segment_batch` segments of a clip go through one
+    generator call, stacked in the batch dimension with the clip's highcut repeated; 1 is the reference's loop."""
+    if wave_input.size(2) <= segment_length:
+        return gen(wave_input, highcut)
+    segs = unfold_audio(wave_input, segment_length, overlap)              # (B, C, n, seg)
+    B, C, n, _ = segs.shape
+    done = torch.zeros_like(segs)
+    for i in range(0, n, segment_batch):
+        k = min(segment_batch, n - i)
+        if k == 1:
+            done[:, :, i] = gen(segs[:, :, i].contiguous(), highcut)
+        else:
+            out = gen(segs[:, :, i:i + k].transpose(1, 2).reshape(B * k, C, segment_length), highcut.repeat_interleave(k))
+            done[:, :, i:i + k] = out.view(B, k, C, segment_length).transpose(1, 2)
+    return fold_audio(done, wave_input.size(2), segment_length, overlap)
 
 
 class BaseTester:
@@ -84,24 +124,15 @@ class Tester(BaseTester):
                              if fused_metrics and self.device.type == "cuda" and all(m in known for m in metric_ftns) else None)
         self.test_loader = data_loader
         self.test_log = {}
-        self.num_frames_per_seg = int(int(config.DATA.SEGMENT * config.DATA.FLAC2WAV.SRC_SR) * self.target_sr
-                                      / config.DATA.FLAC2WAV.SRC_SR)
+        self.num_frames_per_seg = frames_per_segment(config, self.target_sr)
         for k, m in self.models.items():
             self.models[k] = m.to(self.device)
 
     def _sync(self):
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
+        device_sync(self.device)
 
     def _enhance(self, wave_input, highcut):
-        gen = self.models["generator"]
-        if wave_input.size(2) <= self.num_frames_per_seg:
-            return gen(wave_input, highcut)
-        segs = unfold_audio(wave_input, self.num_frames_per_seg, self.config.TEST.OVERLAP)
-        done = torch.zeros_like(segs)
-        for i in range(segs.size(2)):
-            done[:, :, i] = gen(segs[:, :, i].contiguous(), highcut)
-        return fold_audio(done, wave_input.size(2), self.num_frames_per_seg, self.config.TEST.OVERLAP)
+        return enhance(self.models["generator"], wave_input, highcut, self.num_frames_per_seg, self.config.TEST.OVERLAP)
 
     @torch.no_grad()
     def evaluate(self):
@@ -142,12 +173,7 @@ class Tester(BaseTester):
         stem = str(filename[0] if isinstance(filename, (list, tuple)) else filename).replace(".wav", "")
         keep = wave_input.size(2) - pad
         for tag, w in (("up", wave_out), ("orig", wave_target), ("down", wave_input)):
-            pcm = (w[0, 0, :keep].float().clamp(-1, 1) * 32767.0).round().to(torch.int16).cpu().numpy()
-            with wave.open(os.path.join(self.output_dir, f"{stem}_{tag}.wav"), "wb") as f:
-                f.setnchannels(1)
-                f.setsampwidth(2)
-                f.setframerate(int(self.config.DATA.TARGET_SR))
-                f.writeframes(pcm.tobytes())
+            write_pcm16(os.path.join(self.output_dir, f"{stem}_{tag}.wav"), w[0, 0, :keep], self.config.DATA.TARGET_SR)
 
     def save_results_to_csv(self, results, filename="results.csv"):
         """One row per evaluation, the reference's column order (trainer/tester.py:221-240)."""
