@@ -195,6 +195,40 @@ int vmasr_metrics(const float *out, const float *tgt, const int64_t *hf, float *
 int vmasr_resample_poly(const float *x, const float *h, float *y, int32_t B, int64_t n_in, int64_t n_out, int32_t up, int32_t down,
                         int32_t half_len, vmasr_stream_t stream);
 
+/* The filter vmasr_resample_poly expects, designed on the device (csrc/resample.hip): h, 2*half_len+1 fp32 taps, with
+ * fc = 1/max(up,down) and m = i - half_len
+ *     h[i] = up * g[i] / sum(g),   g[i] = fc * sinc(fc*m) * I0(5*sqrt(1 - (m/half_len)^2)) / I0(5)
+ * which is up * firwin(2*half_len+1, fc, window=("kaiser", 5.0)) (vm_asr_amd/resample.py:design; half_len = 10*max(up,down) gives
+ * scipy's default).  Everything is evaluated in float64 and rounded to fp32 once, at the store.  Two launches; the sum is a fixed
+ * two-stage tree without atomics, so the taps are bit-identical from call to call.  No host read.  VMASR_EINVAL, nothing launched:
+ * a null pointer; up or down <= 0; gcd(up,down) != 1; half_len < 1 (or > 2^30); ws smaller than
+ * vmasr_resample_design_workspace(half_len) bytes or not 8-byte aligned.  The query returns 0 for a half_len that is refused. */
+size_t vmasr_resample_design_workspace(int32_t half_len);
+int vmasr_resample_design(float *h, int32_t up, int32_t down, int32_t half_len, void *ws, size_t ws_bytes, vmasr_stream_t stream);
+
+/* One clip of vmasr_degrade_batch: resampled by up/down (taps h_down, 2*half_len+1 of them) to n_mid = ceil(T*up/down) samples,
+ * kept at float offset mid_off of the workspace, and back by down/up (taps h_up, 2*half_len_up+1).  up == down (== 1): the clip is
+ * copied; its taps and mid_off are not read. */
+typedef struct vmasr_degrade_item {
+    const float *h_down, *h_up;     /* device pointers, taps already multiplied by the pass's `up` (as for vmasr_resample_poly) */
+    int64_t n_mid, mid_off;
+    int32_t up, down, half_len, half_len_up;
+} vmasr_degrade_item;
+/* The reference's low-resolution input of B clips at per-clip rates (data_loader/data_loaders.py:424-488,523-535) in two launches
+ * (csrc/resample.hip): x (B,T) fp32 -> y (B,T) fp32, row b = vmasr_resample_poly by up_b/down_b, again by down_b/up_b, then
+ * trimmed to T or zero-filled up to T (align_waveform).  The down pass writes every clip's intermediate to the workspace, the up
+ * pass writes y.  Each output sums the terms of vmasr_resample_poly in its order, so with the same taps a row is bit-identical to
+ * the two single-ratio calls.  Every workgroup takes its own clip's staging (input window / taps in LDS or read from global
+ * memory); every accepted combination is computed.  `items`: the B descriptors in HOST memory, read by the launcher (checks, grid,
+ * LDS size); `items_dev`: the same bytes on the device, read by the kernels.  Intermediates lie in clip order, 16-byte aligned,
+ * without overlap; vmasr_degrade_batch_workspace gives the bytes of the tightest such layout.  VMASR_EINVAL, nothing launched:
+ * a null pointer (ws only when some clip is resampled); B <= 0 or B > 65535; T <= 0; up or down <= 0 or not coprime;
+ * n_mid != ceil(T*up/down); null taps or a negative half_len of a resampled clip; an intermediate outside ws_bytes, misaligned
+ * or overlapping its predecessor; sizes past the 64-bit index arithmetic. */
+size_t vmasr_degrade_batch_workspace(const vmasr_degrade_item *items, int32_t B);
+int vmasr_degrade_batch(const float *x, float *y, const vmasr_degrade_item *items, const vmasr_degrade_item *items_dev, int32_t B,
+                        int64_t T, void *ws, size_t ws_bytes, vmasr_stream_t stream);
+
 /* Channel-last LayerNorm over the last dimension (F.layer_norm on (rows, C) with C <= 1024):
  * SS2D.out_norm, VSSBlock.norm/norm2, PatchMerging2D.norm, PatchExpanding.norm
  * (model/vmamba.py:767-769,1793,1817; model/model.py:70,105-108,620,631).
@@ -697,6 +731,8 @@ enum {
     VMASR_K_WGRAD_FINISH,       /* sum over split-K slabs + bias column split-off of many weight gradients, one launch (csrc/wgrad.hip) */
     VMASR_K_SKINNY_LINEAR,      /* y = x W^T + b for >= 4096 rows and <= 96 features each side (csrc/skinny.hip) */
     VMASR_K_METRICS,            /* SNR / LSD / LSD-HF / LSD-LF of a batch: packed out/tgt FFT per frame + finish (csrc/metrics.hip) */
+    VMASR_K_RESAMPLE_DESIGN,    /* resampling filter designed on the device: taps + partial sums, normalise (csrc/resample.hip) */
+    VMASR_K_DEGRADE_BATCH,      /* a batch degraded at per-clip rates: down pass, up pass + align (csrc/resample.hip) */
     VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };

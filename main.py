@@ -4,11 +4,15 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --cfg ... --synthetic 512
     python main.py --cfg ... --eval --resume logs/.../ --tag 16000_48000 --synthetic 8 --degrade
     python main.py --cfg ... --inference --input speech.wav --resume logs/.../ --tag 16000_48000     # or --input <directory>
+    python main.py --cfg ... --data-path data/                                      # train on <data>/<DST_PATH>/<speaker>/*.wav
+    python main.py --cfg ... --data-path data/ --eval --resume logs/.../ --tag 16000_48000
 
 `--cfg` takes the reference's yaml files unchanged.  The VCTK pipeline (download, flac decoding, dataset splits:
 data_loader/data_loaders.py) is out of scope: clips come from `--synthetic N` (trainer.SyntheticVCTK, the
 reference's batch contract) — a real dataset plugs in as any DataLoader yielding `(wave_in, wave_tgt, highcut, name,
-pad)`.  `--degrade` replaces each clip's input by the reference's degradation of its target, computed on the device
+pad)`.  `--data-path DIR` sets DATA.DATA_PATH and takes the clips from the wav files below it instead (vm_asr_amd.data: the
+reference's speaker split, validation split and test loader; resampling, noise tail and the input degradation run on the
+device); it excludes `--synthetic`.  `--degrade` replaces each clip's input by the reference's degradation of its target, computed on the device
 (vm_asr_amd.resample.DegradeOnDevice: resampled down and up again; the rate is TAG's under --eval, a seeded draw from
 DATA.RANDOM_RESAMPLE per clip in training).  `--inference --input <wav file or directory>` enhances wav files
 (vm_asr_amd.inferencer) and writes `{stem}_enhanced.wav`; `--throughput` runs bench.py's measurement.
@@ -43,7 +47,9 @@ def parse_option(argv=None):
     p.add_argument("--inference", action="store_true")
     p.add_argument("--input", type=str)
     p.add_argument("--throughput", action="store_true")
-    p.add_argument("--synthetic", type=int, default=64, help="number of synthetic VCTK-shaped clips per epoch")
+    p.add_argument("--synthetic", type=int, default=None, help="number of synthetic VCTK-shaped clips per epoch (default 64)")
+    p.add_argument("--data-path", type=str, metavar="DIR",
+                   help="train / evaluate on the wav files of DIR/<DATA.FLAC2WAV.DST_PATH>/<speaker>/ (vm_asr_amd.data) instead of synthetic clips")
     p.add_argument("--epochs", type=int, help="override TRAIN.EPOCHS")
     p.add_argument("--no-graphs", action="store_true", help="run the step eagerly instead of replaying HIP graphs")
     p.add_argument("--degrade", action="store_true",
@@ -52,8 +58,14 @@ def parse_option(argv=None):
     p.add_argument("--step-metrics", action="store_true",
                    help="metrics on every step / clip through the fused kernel (Trainer step_metrics, Tester fused_metrics)")
     args = p.parse_args(argv)
+    if args.data_path and args.synthetic is not None:
+        p.error("--data-path and --synthetic exclude each other")
+    if args.synthetic is None:
+        args.synthetic = 64
     from vm_asr_amd.config import get_config
     opts = list(args.opts or [])
+    if args.data_path:
+        opts += ["DATA.DATA_PATH", args.data_path]
     if args.target_sr:
         opts += ["DATA.TARGET_SR", args.target_sr]
     if args.epochs:
@@ -93,21 +105,30 @@ def main(args, config):
     sr_in = args.input_sr or (16000 if config.DATA.TARGET_SR == 48000 else 8000)
     if config.EVAL_MODE:
         from vm_asr_amd.tester import Tester
-        ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 10_000)
-        loader = torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False)
-        if args.degrade:
+        if args.data_path:
+            from vm_asr_amd.data import get_loader
+            loader = get_loader(config, device, log)
+        else:
+            ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 10_000)
+            loader = torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False)
+        if args.degrade and not args.data_path:
             from vm_asr_amd.resample import DegradeOnDevice
             loader = DegradeOnDevice(loader, config, device, sr_input=int(str(config.TAG).split("_")[0]))
         res = Tester({"generator": models["generator"]}, metrics, config, device, loader, log, fused_metrics=args.step_metrics).evaluate()
         print({k: round(v, 4) if isinstance(v, float) else v for k, v in res.items()})
         return
-    ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 1000 * rank)
-    loader = torch.utils.data.DataLoader(ds, batch_size=config.DATA.BATCH_SIZE, shuffle=False, drop_last=True)
-    if args.degrade:
-        from vm_asr_amd.resample import DegradeOnDevice
-        loader = DegradeOnDevice(loader, config, device, seed=config.SEED + 1000 * rank)
     gan = config.TRAIN.ADVERSARIAL.ENABLE
     graphs = not args.no_graphs and config.TRAIN.ACCUMULATION_STEPS == 1
+    val_loader = None
+    if args.data_path:
+        from vm_asr_amd.data import get_loader
+        loader, val_loader = get_loader(config, device, log, drop_last=graphs)
+    else:
+        ds = SyntheticVCTK(config, length=args.synthetic, sr_in=sr_in, seed=config.SEED + 1000 * rank)
+        loader = torch.utils.data.DataLoader(ds, batch_size=config.DATA.BATCH_SIZE, shuffle=False, drop_last=True)
+        if args.degrade:
+            from vm_asr_amd.resample import DegradeOnDevice
+            loader = DegradeOnDevice(loader, config, device, seed=config.SEED + 1000 * rank)
     for m in models.values():
         if m is not None:
             m.to(device)
@@ -117,7 +138,7 @@ def main(args, config):
     steps = max(1, len(loader) // config.TRAIN.ACCUMULATION_STEPS)
     sched = {k: CosineWarmupScheduler(o, config.TRAIN.EPOCHS * steps, config.TRAIN.WARMUP_EPOCHS * steps, config.TRAIN.BASE_LR,
                                       config.TRAIN.MIN_LR, config.TRAIN.LR_SCHEDULER.WARMUP_PREFIX) for k, o in opts.items()}
-    tr = Trainer(models, metrics, opts, config, device, loader, None, sched, amp=config.AMP_ENABLE, gan=gan, logger=log,
+    tr = Trainer(models, metrics, opts, config, device, loader, val_loader, sched, amp=config.AMP_ENABLE, gan=gan, logger=log,
                  step_metrics=args.step_metrics)
     if graphs:
         first = next(iter(loader))

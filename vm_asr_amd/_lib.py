@@ -202,6 +202,10 @@ SYMBOLS = {
     "vmasr_metrics_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_metrics": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "vmasr_resample_poly": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "vmasr_resample_design_workspace": (c_sz, [c_i32]),
+    "vmasr_resample_design": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "vmasr_degrade_batch_workspace": (c_sz, [c_vp, c_i32]),
+    "vmasr_degrade_batch": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_sz, c_vp]),
 }
 
 _lib = None
@@ -322,7 +326,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 62
+K_COUNT = 64
 
 
 def zeros_f32(device, *shapes):

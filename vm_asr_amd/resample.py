@@ -4,6 +4,8 @@
     resample_poly(x, up, down)    -> (..., ceil(T*up/down))          scipy.signal.resample_poly(x, up, down, axis=-1)
     degrade(wave, sr, sr_input)   -> wave's shape                    down to sr_input, up again, align_waveform
     DegradeOnDevice(loader, ...)                                     any loader's wave_in replaced by degrade(target)
+    design_on_device(up, down, device) -> fp32 taps on `device`      the same filter designed by the library, no host work
+    degrade_batch(waves, sr, rates)    -> waves' shape               degrade() of every clip at its own rate, two launches
 
 The reference makes every low-resolution input on the CPU with scipy, one clip at a time: resample the target down to the
 input rate and up again (data_loader/data_loaders.py:424-488 `_get_io_pair`; the low-pass result computed there is overwritten
@@ -28,7 +30,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["design", "resample_poly", "degrade", "highcut_bin", "DegradeOnDevice"]
+__all__ = ["design", "resample_poly", "degrade", "highcut_bin", "DegradeOnDevice", "design_on_device", "degrade_batch"]
 
 
 def _reduced(up, down):
@@ -148,3 +150,101 @@ class DegradeOnDevice:
             wave_in = torch.stack([degrade(tgt[i], self.target_sr, r) for i, r in enumerate(rates)])
             highcut = torch.tensor([highcut_bin(self.config, r) for r in rates], dtype=torch.int64)
             yield wave_in, tgt, highcut, name, pad
+
+
+# ---- a batch at per-clip rates: filters designed on the device, two launches (csrc/resample.hip) ----------------------------------------
+# The random rates of training rarely repeat (40 001 possible at 48 kHz), so the host design of `_taps` (75 ms for a rate coprime
+# to 48 000: profiles/resample.md) is replaced by one library call per direction, and the clips of a batch share two launches
+# instead of two launches, a pad or slice and a stack each (profiles/datapipe.md has the measured difference).
+
+_designed = collections.OrderedDict()        # (up, down, device) -> fp32 taps designed on that device, least recently used first
+
+_ITEM = np.dtype([("h_down", "u8"), ("h_up", "u8"), ("n_mid", "i8"), ("mid_off", "i8"), ("up", "i4"), ("down", "i4"),
+                  ("half_len", "i4"), ("half_len_up", "i4")])            # vmasr_degrade_item (include/vmasr_hip.h)
+
+
+@torch.no_grad()
+def design_on_device(up, down, device):
+    """The 2*half_len + 1 fp32 taps of `design(up, down)` (half_len = 10*max(up, down) of the reduced ratio) on the GPU `device`,
+    computed there in float64 by one library call: no host design, no copy.  The CACHE_RATIOS most recently used ratios per
+    process are kept; an evicted filter is freed once the launches that read it have run (a user on another stream than the
+    one it was designed on records that stream, as degrade_batch does)."""
+    up, down = _reduced(up, down)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("design_on_device: expected a CUDA (HIP) device; vm_asr_amd has no CPU path")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (up, down, device)
+    h = _designed.get(key)
+    if h is not None:
+        _designed.move_to_end(key)
+        return h
+    half_len = 10 * max(up, down)
+    lib = _lib.lib()
+    ws_bytes = lib.vmasr_resample_design_workspace(half_len)
+    with torch.cuda.device(device):
+        h = torch.empty(2 * half_len + 1, dtype=torch.float32, device=device)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    _lib.call(lib.vmasr_resample_design, h, up, down, half_len, ws, ws_bytes)
+    _designed[key] = h
+    while len(_designed) > CACHE_RATIOS:
+        _designed.popitem(last=False)
+    return h
+
+
+@torch.no_grad()
+def degrade_batch(waves, sr, rates, taps=None):
+    """waves (B, T) or (B, 1, T) fp32 on the GPU -> the same shape: row b is degrade(waves[b], sr, rates[b]) — down to rates[b],
+    up to `sr` again, trimmed or zero-filled to T; a clip whose rate equals `sr` is copied — for the whole batch in one library
+    call of two launches.  `taps`: {(up, down) reduced: fp32 taps on waves' device} for both directions of every ratio used
+    (given the taps degrade() uses, a row is bit-identical to it); absent, every distinct direction is designed on the device
+    (design_on_device) once.  No autograd, no CPU path; RuntimeError on misuse."""
+    _lib.require_cuda("degrade_batch", waves)
+    if waves.dtype != torch.float32:
+        raise RuntimeError(f"degrade_batch: expected float32, got {waves.dtype}")
+    if not (waves.dim() == 2 or (waves.dim() == 3 and waves.shape[1] == 1)) or waves.numel() == 0:
+        raise RuntimeError(f"degrade_batch: expected (B, T) or (B, 1, T) with B, T >= 1, got {tuple(waves.shape)}")
+    B, T = waves.shape[0], waves.shape[-1]
+    rates = [int(r) for r in rates]
+    if len(rates) != B:
+        raise RuntimeError(f"degrade_batch: {len(rates)} rates for {B} clips")
+    ratios = [_reduced(r, sr) for r in rates]                  # (up, down) of the down pass; RuntimeError for a rate <= 0
+    stream = torch.cuda.current_stream(waves.device)
+    filt = {}
+
+    def taps_of(up, down):
+        h = filt.get((up, down))
+        if h is None:
+            if taps is None:
+                h = design_on_device(up, down, waves.device)
+                h.record_stream(stream)                        # (a no-op on the stream it was designed on)
+            else:
+                h = taps.get((up, down))
+                if h is None:
+                    raise RuntimeError(f"degrade_batch: taps= has no filter for the ratio {up}/{down}")
+                if not (h.is_cuda and h.device == waves.device and h.dtype == torch.float32 and h.dim() == 1 and h.is_contiguous()
+                        and h.numel() % 2 == 1):
+                    raise RuntimeError(f"degrade_batch: taps[{(up, down)}] must be an odd number of contiguous fp32 taps on {waves.device}")
+            filt[(up, down)] = h
+        return h
+
+    items, off = np.zeros(B, dtype=_ITEM), 0
+    for b, (up, down) in enumerate(ratios):
+        n_mid = -(-T * up // down)
+        items[b]["up"], items[b]["down"], items[b]["n_mid"] = up, down, n_mid
+        if up != down:
+            hd, hu = taps_of(up, down), taps_of(down, up)
+            items[b]["h_down"], items[b]["h_up"] = hd.data_ptr(), hu.data_ptr()
+            items[b]["half_len"], items[b]["half_len_up"] = (hd.numel() - 1) // 2, (hu.numel() - 1) // 2
+            items[b]["mid_off"] = off
+            off += -(-n_mid // 4) * 4
+    x = _lib.rows2d(waves, T)
+    lib = _lib.lib()
+    host = items.ctypes.data
+    ws_bytes = lib.vmasr_degrade_batch_workspace(host, B)
+    y = torch.empty_like(x)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    table = torch.from_numpy(items.view(np.uint8)).to(x.device)
+    _lib.call(lib.vmasr_degrade_batch, x, y, host, table, B, T, ws, ws_bytes)
+    return y.view(waves.shape)
