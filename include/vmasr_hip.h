@@ -338,6 +338,11 @@ int vmasr_bias_gelu_fwd(float *acc, const float *bias, float *act, int32_t slots
 /* w (n, N, K) fp32 -> out (n, K, 3N) bf16 = [hi^T | hi^T | lo^T] of the bf16 split of w: the B operands of the
  * forward GEMM triple (column blocks 0 and 2) and of the concatenated-contraction column-gradient GEMM (all of it) */
 int vmasr_weight_prep_split(const float *w, void *out, int32_t n, int32_t N, int32_t K, vmasr_stream_t stream);
+/* w (n, N, k, Cin) fp32 (the forward operand, (tap, channel) columns) -> the input gradient's operand (n, Cin, k*N) in (tap, output
+ * channel) order, out[s, c, j*N + o] = w[s, o, j, c]: as the bf16 pair hi, lo (vmasr_split_bf16's) and / or as fp32 out32, one pass
+ * through LDS tiles.  Cin % 4 == 0, N % 8 == 0. */
+int vmasr_weight_transpose(const float *w, void *hi, void *lo, float *out32, int32_t n, int32_t N, int32_t Cin, int32_t k,
+                           vmasr_stream_t stream);
 /* out (n, NK) = sum over p < P, s < S of parts (P, n, S, NK): the partial products of a split weight-gradient GEMM triple */
 int vmasr_sum_parts(const float *parts, float *out, int32_t P, int32_t n, int32_t S, int64_t NK, vmasr_stream_t stream);
 int vmasr_gelu_bwd_split(const float *pre, const float *g, void *hi, void *lo, void *cat3, float *db, int32_t slots, int64_t M,
@@ -449,11 +454,12 @@ int vmasr_adamw_step(const vmasr_adamw_item *items, const int32_t *chunks, int32
 /* Spectrally normalised weights of one discriminator layer, stacked for the batched pass (model/discriminator.py:26-45:
  * spectral_norm around every convolution; sigma, u, v from the power iteration are constants for autograd):
  *   fwd: out (n, N, k*Cin) with out[s, o, j*Cin + c] = W_s[o, c, j] / sigma_s   (W_s: (N, Cin, k) fp32, HOST array of n pointers)
+ *        hi, lo (both or neither, may be NULL): the bf16 pair of out (vmasr_split_bf16's), same shape, written in the same pass
  *   bwd: gW_s[o, c, j] = (dW[s, o, j*Cin + c] - <dW_s, Wn_s> u_s[o] v_s[c*k + j]) / sigma_s, Wn = the forward's output;
  *        partials: n * vmasr_sn_dot_blocks() doubles of scratch.  sigmas / us / vs / gws: HOST arrays of device pointers. */
 int32_t vmasr_sn_dot_blocks(void);
-int vmasr_sn_stack_fwd(const void *const *weights, const void *const *sigmas, int32_t n, float *out, int32_t N, int32_t Cin, int32_t k,
-                       vmasr_stream_t stream);
+int vmasr_sn_stack_fwd(const void *const *weights, const void *const *sigmas, int32_t n, float *out, void *hi, void *lo, int32_t N, int32_t Cin,
+                       int32_t k, vmasr_stream_t stream);
 int vmasr_sn_stack_bwd(const float *dW, const float *Wn, void *const *gws, const void *const *sigmas, const void *const *us,
                        const void *const *vs, int32_t n, double *partials, int32_t N, int32_t Cin, int32_t k, vmasr_stream_t stream);
 
@@ -467,6 +473,14 @@ int vmasr_conv_post_fwd(const float *x, const float *w, const float *b, float *y
                         int32_t C, int32_t k, vmasr_stream_t stream);
 int vmasr_conv_post_bwd(const float *x, const float *w, const float *gy, float *dx, float *dw, float *db, const int64_t *Ms, const int32_t *Hs,
                         int32_t n, int64_t rows, int32_t C, int32_t k, vmasr_stream_t stream);
+/* vmasr_conv_post_bwd with the activation backward of the layer below in it: g = (dx + gtok[0] scale[s] sgn) GELU'(pre), the sign term
+ * (sgn (n, rows, C) int8, optional; gtok a device scalar; valid / scale HOST arrays) on the rows < valid[s].  pre (n, rows, C) fp32: that
+ * layer's pre-activation.  Written: the bf16 pair gh, gl (n, rows, C) of g and / or g32 (fp32), zeros on the rows >= Ms[s]; dx itself
+ * never.  dbcol (n, C), zeroed by the caller: += the column sums of g (that layer's bias gradient).  dw (n, 3, C) / db (n): conv_post's
+ * own, as above; x is read only with dw (else it may be NULL).  gh + gl, g32, sgn, dw, db, dbcol may each be NULL (gh or g32 is required). */
+int vmasr_conv_post_bwd_gelu(const float *x, const float *w, const float *gy, const float *pre, const void *sgn, const float *gtok,
+                             const int64_t *valid, const float *scale, void *gh, void *gl, float *g32, float *dw, float *db, float *dbcol,
+                             const int64_t *Ms, const int32_t *Hs, int32_t n, int64_t rows, int32_t C, int32_t k, vmasr_stream_t stream);
 
 /* First convolution of the period discriminators (model/discriminator.py:26-40,100-104: Conv2d(1, 32, (5,1), (3,1), padding
  * (2,0)) + GELU) for all n discriminators in one launch: xs[s] (Ns[s] sequences x Hs[s] samples, fp32; HOST arrays),
@@ -714,6 +728,8 @@ enum {
     VMASR_K_FEAT_L1,            /* feature-matching loss over the stacked feature maps, fwd + bwd   */
     VMASR_K_ADAMW,              /* AdamW step of all parameters (+ bf16 shadow refresh), one launch */
     VMASR_K_CONV_POST,          /* the discriminators' 1024 -> 1 output convolution on the stacked maps */
+    VMASR_K_CONV_POST_BWD_GELU, /* its backward with the activation backward of the layer below in it (GELU', sign term, bf16 pair, bias sums) */
+    VMASR_K_WEIGHT_T,           /* (n, Cout, k, Cin) fp32 weight operand -> the input gradient's (n, Cin, k*Cout) operand, bf16 pair or fp32 */
     VMASR_K_MLP_FWD,            /* LayerNorm + fc1 + GELU + fc2 + residual of a VSS block as one MFMA kernel */
     VMASR_K_MLP_BWD,
     VMASR_K_INPROJ_FWD,         /* LayerNorm + in_proj + chunk + SiLU(z) + channel-first copy of a VSS block's SS2D as one MFMA kernel */

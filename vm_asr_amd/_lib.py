@@ -124,11 +124,12 @@ SYMBOLS = {
     "vmasr_bias_gelu_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),
     "vmasr_gelu_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "vmasr_sn_dot_blocks": (c_i32, []),
-    "vmasr_sn_stack_fwd": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "vmasr_sn_stack_fwd": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_sn_stack_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_conv_post_supported": (ctypes.c_int, [c_i32, c_i32]),
     "vmasr_conv_post_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),
     "vmasr_conv_post_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_vp]),
+    "vmasr_conv_post_bwd_gelu": (ctypes.c_int, [c_vp] * 16 + [c_i32, c_i64, c_i32, c_i32, c_vp]),
     "vmasr_conv_first_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "vmasr_conv_first_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "vmasr_adamw_chunk": (c_i32, []),
@@ -141,6 +142,7 @@ SYMBOLS = {
     "vmasr_masked_l1_bwd_add": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "vmasr_sum_parts": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_vp]),
     "vmasr_weight_prep_split": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "vmasr_weight_transpose": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_gelu_bwd_split": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "vmasr_conv_mfma_supported": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_conv_mfma_supported_launch": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_int64]),
@@ -326,7 +328,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 64
+K_COUNT = 66
 
 
 def zeros_f32(device, *shapes):

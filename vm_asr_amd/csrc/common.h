@@ -60,6 +60,18 @@ template <typename T> __device__ __forceinline__ T from_f32(float v) { return (T
 
 constexpr int kWave = 64;
 
+// error-compensated bf16 pair of an fp32 value: x = hi + lo up to 2^-17 |x| (csrc/split.hip)
+__device__ __forceinline__ void split1(float x, bf16_t &hi, bf16_t &lo) {
+    hi = (bf16_t)x;                    // round to nearest even (v_cvt_pk_bf16_f32)
+    lo = (bf16_t)(x - (float)hi);      // exact difference, rounded once
+}
+
+// exact (erf) GELU and its derivative, torch's default form
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_grad_f(float x) {
+    return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
+}
+
 // 4 consecutive elements starting at p[t] (t may run past `len`; out-of-range -> fill).
 // VEC: p + t is 4-element aligned and the caller guarantees 16-B (fp32) / 8-B (16-bit)
 // alignment of the row base, so a full quad is one dwordx4 / dwordx2 load.

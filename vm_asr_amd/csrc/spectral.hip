@@ -257,7 +257,10 @@ struct SnSlots {
     const float *v[kSnMaxSlots];       // (Cin * k)
 };
 
-__global__ __launch_bounds__(256) void sn_stack_fwd_kernel(const SnSlots t, float *__restrict__ out, const int N, const int Cin, const int k) {
+// hi / lo (optional): the bf16 pair of out (split1, common.h) — the MFMA convolutions' weight operand, written here instead of by a
+// split_bf16 pass that reads out again
+__global__ __launch_bounds__(256) void sn_stack_fwd_kernel(const SnSlots t, float *__restrict__ out, bf16_t *__restrict__ hi,
+                                                           bf16_t *__restrict__ lo, const int N, const int Cin, const int k) {
     extern __shared__ float row[];
     const int s = blockIdx.y, o = blockIdx.x, K = Cin * k;
     const float inv = 1.f / t.sigma[s][0];
@@ -265,7 +268,16 @@ __global__ __launch_bounds__(256) void sn_stack_fwd_kernel(const SnSlots t, floa
     for (int i = threadIdx.x; i < K; i += 256) row[i] = src[i] * inv;          // (c, j) order
     __syncthreads();
     float *dst = out + ((size_t)s * N + o) * K;
-    for (int e = threadIdx.x; e < K; e += 256) dst[e] = row[(e % Cin) * k + e / Cin];   // (j, c) order
+    if (hi == nullptr) {
+        for (int e = threadIdx.x; e < K; e += 256) dst[e] = row[(e % Cin) * k + e / Cin];   // (j, c) order
+        return;
+    }
+    bf16_t *dh = hi + ((size_t)s * N + o) * K, *dl = lo + ((size_t)s * N + o) * K;
+    for (int e = threadIdx.x; e < K; e += 256) {
+        const float v = row[(e % Cin) * k + e / Cin];
+        dst[e] = v;
+        split1(v, dh[e], dl[e]);
+    }
 }
 
 __global__ __launch_bounds__(256) void sn_dot_kernel(const float *__restrict__ dW, const float *__restrict__ Wn, double *__restrict__ partials,
@@ -327,15 +339,16 @@ using namespace vmasr;
 
 VMASR_EXPORT int32_t vmasr_sn_dot_blocks(void) { return kSnDotBlocks; }
 
-VMASR_EXPORT int vmasr_sn_stack_fwd(const void *const *weights, const void *const *sigmas, int32_t n, float *out, int32_t N, int32_t Cin,
-                                    int32_t k, vmasr_stream_t stream) {
+VMASR_EXPORT int vmasr_sn_stack_fwd(const void *const *weights, const void *const *sigmas, int32_t n, float *out, void *hi, void *lo, int32_t N,
+                                    int32_t Cin, int32_t k, vmasr_stream_t stream) {
     VMASR_REQUIRE(weights && sigmas && out, VMASR_EINVAL, "sn_stack_fwd: null argument");
+    VMASR_REQUIRE((hi && lo) || (!hi && !lo), VMASR_EINVAL, "sn_stack_fwd: the bf16 pair needs both hi and lo");
     VMASR_REQUIRE(N > 0 && N <= 65535 && Cin > 0 && k > 0 && (size_t)Cin * k * 4 <= 60 * 1024, VMASR_EINVAL, "sn_stack_fwd: bad shape");
     SnSlots t{};
     if (int e = sn_fill(t, weights, nullptr, sigmas, nullptr, nullptr, n, "sn_stack_fwd")) return e;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    VMASR_LAUNCH(VMASR_K_SPECTRAL, 8.0 * n * (double)N * Cin * k, sn_stack_fwd_kernel, dim3(N, n), dim3(256), (size_t)Cin * k * 4, st, t, out, N,
-                 Cin, k);
+    VMASR_LAUNCH(VMASR_K_SPECTRAL, (hi ? 12.0 : 8.0) * n * (double)N * Cin * k, sn_stack_fwd_kernel, dim3(N, n), dim3(256), (size_t)Cin * k * 4, st,
+                 t, out, static_cast<bf16_t *>(hi), static_cast<bf16_t *>(lo), N, Cin, k);
     return check_launch("sn_stack_fwd");
 }
 

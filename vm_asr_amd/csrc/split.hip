@@ -16,11 +16,6 @@
 namespace vmasr {
 namespace {
 
-__device__ __forceinline__ void split1(float x, bf16_t &hi, bf16_t &lo) {
-    hi = (bf16_t)x;                    // round to nearest even (v_cvt_pk_bf16_f32)
-    lo = (bf16_t)(x - (float)hi);      // exact difference, rounded once
-}
-
 __global__ __launch_bounds__(256) void split_bf16_kernel(const float *__restrict__ x, bf16_t *__restrict__ hi,
                                                          bf16_t *__restrict__ lo, const size_t n8, const size_t n) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -64,11 +59,7 @@ VMASR_EXPORT int vmasr_split_bf16(const float *x, void *hi, void *lo, int64_t n,
 namespace vmasr {
 namespace {
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x) {
-    return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
+// (split1, gelu_f, gelu_grad_f: common.h)
 // grid: (row chunks, slots); block 256 threads; each thread owns 4 consecutive columns of one or more rows per pass.
 // acc is (parts, slots, M, N): the pre-activation is the SUM of the parts (the three products of an error-compensated
 // GEMM triple, written side by side instead of accumulated by two read-modify-write passes) + bias, stored into part 0.
@@ -116,6 +107,51 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const float *__restric
             split1(tile[tx][r], h, l);
             bf16_t *row = dst + (size_t)k * 3 * N;
             row[o] = h; row[N + o] = h; row[2 * N + o] = l;
+        }
+    }
+}
+
+// Input-gradient operand of the implicit-GEMM convolutions: w (n, N, k, Cin) fp32 — the forward operand, (tap, channel) columns — ->
+// (n, Cin, k * N) in (tap, output channel) order, out[s, c, j N + o] = w[s, o, j, c], as the bf16 pair (hi, lo) or as fp32 (out32).
+// One pass (r 4, w 4 B/elt) instead of a strided transpose copy (r 4, w 4) + split_bf16 (r 4, w 4).  Per tap a 64 x 64 tile of the
+// (N x Cin) matrix goes through LDS: 16-byte reads along c, 16-byte writes along o.  grid (Cin tiles, N tiles, n * k); Cin % 4 == 0, N % 8 == 0.
+__global__ __launch_bounds__(256) void weight_transpose_kernel(const float *__restrict__ w, bf16_t *__restrict__ hi, bf16_t *__restrict__ lo,
+                                                               float *__restrict__ out32, const int N, const int Cin, const int k) {
+    __shared__ float tile[64][65];      // [o][c]
+    const int slot = blockIdx.z / k, j = blockIdx.z % k, c0 = blockIdx.x * 64, o0 = blockIdx.y * 64;
+    const float *src = w + (size_t)slot * N * k * Cin + (size_t)j * Cin;                 // row o: + o * k * Cin
+    const size_t obase = (size_t)slot * Cin * k * N + (size_t)j * N;                     // row c: + c * k * N
+    {
+        const int tc = (threadIdx.x % 16) * 4, tr = threadIdx.x / 16;                    // 16 rows of 16 float4 per pass
+        for (int r = tr; r < 64; r += 16) {
+            const int o = o0 + r, c = c0 + tc;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (o < N && c < Cin) v = *reinterpret_cast<const float4 *>(src + (size_t)o * k * Cin + c);
+            tile[r][tc] = v.x; tile[r][tc + 1] = v.y; tile[r][tc + 2] = v.z; tile[r][tc + 3] = v.w;
+        }
+    }
+    __syncthreads();
+    if (out32) {
+        const int to = (threadIdx.x % 16) * 4, tr = threadIdx.x / 16;
+        for (int r = tr; r < 64; r += 16) {                                             // r: c within the tile
+            const int c = c0 + r, o = o0 + to;
+            if (c < Cin && o < N)
+                *reinterpret_cast<float4 *>(out32 + obase + (size_t)c * k * N + o) =
+                    make_float4(tile[to][r], tile[to + 1][r], tile[to + 2][r], tile[to + 3][r]);
+        }
+    }
+    if (hi) {
+        const int to = (threadIdx.x % 8) * 8, tr = threadIdx.x / 8;                      // 32 rows of 8 x 16 bytes per pass
+        for (int r = tr; r < 64; r += 32) {
+            const int c = c0 + r, o = o0 + to;
+            if (c < Cin && o < N) {
+                union { uint4 raw; bf16_t e[8]; } h, l;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) split1(tile[to + q][r], h.e[q], l.e[q]);
+                const size_t at = obase + (size_t)c * k * N + o;
+                *reinterpret_cast<uint4 *>(hi + at) = h.raw;
+                *reinterpret_cast<uint4 *>(lo + at) = l.raw;
+            }
         }
     }
 }
@@ -227,6 +263,20 @@ VMASR_EXPORT int vmasr_weight_prep_split(const float *w, void *out, int32_t n, i
     hipStream_t st = static_cast<hipStream_t>(stream);
     VMASR_LAUNCH(VMASR_K_SPLIT_BF16, 10.0 * n * (double)N * K, weight_prep_kernel, grid, dim3(256), 0, st, w, static_cast<bf16_t *>(out), N, K);
     return check_launch("weight_prep_split");
+}
+
+VMASR_EXPORT int vmasr_weight_transpose(const float *w, void *hi, void *lo, float *out32, int32_t n, int32_t N, int32_t Cin, int32_t k,
+                                        vmasr_stream_t stream) {
+    VMASR_REQUIRE(w && ((hi && lo) || (!hi && !lo)) && (hi || out32), VMASR_EINVAL, "weight_transpose: null tensor (w, and hi + lo or out32)");
+    VMASR_REQUIRE(n > 0 && N > 0 && Cin > 0 && k > 0 && Cin % 4 == 0 && N % 8 == 0 && (int64_t)n * k <= 65535 && (N + 63) / 64 <= 65535,
+                  VMASR_EINVAL, "weight_transpose: bad shape (n=%d N=%d Cin=%d k=%d: Cin %% 4 == 0, N %% 8 == 0)", n, N, Cin, k);
+    VMASR_REQUIRE(aligned_to(w, 16) && (!hi || (aligned_to(hi, 16) && aligned_to(lo, 16))) && (!out32 || aligned_to(out32, 16)), VMASR_EINVAL,
+                  "weight_transpose: unaligned");
+    const dim3 grid((Cin + 63) / 64, (N + 63) / 64, n * k);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    VMASR_LAUNCH(VMASR_K_WEIGHT_T, (4.0 + (hi ? 4.0 : 0.0) + (out32 ? 4.0 : 0.0)) * n * (double)N * Cin * k, weight_transpose_kernel, grid, dim3(256),
+                 0, st, w, static_cast<bf16_t *>(hi), static_cast<bf16_t *>(lo), out32, N, Cin, k);
+    return check_launch("weight_transpose");
 }
 
 VMASR_EXPORT int vmasr_bias_gelu_fwd(float *acc, const float *bias, float *act, int32_t slots, int64_t M, int32_t N, int32_t parts,

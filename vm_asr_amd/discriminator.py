@@ -115,27 +115,32 @@ class _SNStackFn(torch.autograd.Function):
     """The spectrally normalised weights of one layer of all n period discriminators as ONE (n, N, k*Cin) GEMM operand in
     (tap, channel) column order: out[s] = permute(W_s / sigma_s) with sigma_s, u_s, v_s from the batched power iteration
     (constants, as in torch's spectral_norm).  One launch forward, two backward (csrc/spectral.hip) instead of n divisions +
-    a stack and, per weight, a dot product, an outer-product update and a division."""
+    a stack and, per weight, a dot product, an outer-product update and a division.  An optional last argument, a dict, asks the forward
+    launch for the bf16 pair of the operand too (the MFMA convolutions' weight operand, left in it as "w")."""
 
     @staticmethod
     def forward(ctx, n, *args):
-        sig, us, vs, ws = args[:n], args[n:2 * n], args[2 * n:3 * n], args[3 * n:]
-        out = bind.sn_stack_fwd([w.detach().contiguous() for w in ws], sig)
+        sig, us, vs, ws = args[:n], args[n:2 * n], args[2 * n:3 * n], args[3 * n:4 * n]
+        pair_out = args[4 * n] if len(args) > 4 * n else None
+        out = bind.sn_stack_fwd([w.detach().contiguous() for w in ws], sig, want_pair=pair_out is not None)
+        if pair_out is not None:
+            out, pair_out["w"] = out
         ctx.save_for_backward(out, *sig, *us, *vs)
-        ctx.geom = (n, [w.shape for w in ws])
+        ctx.geom = (n, [w.shape for w in ws], len(args) - 4 * n)
         return out
 
     @staticmethod
     def backward(ctx, dW):
-        n, shapes = ctx.geom
+        n, shapes, extra = ctx.geom
         out, *rest = ctx.saved_tensors
         gws = bind.sn_stack_bwd(dW.float().contiguous(), out, rest[:n], rest[n:2 * n], rest[2 * n:3 * n], shapes)
-        return (None, *([None] * (3 * n)), *gws)
+        return (None, *([None] * (3 * n)), *gws, *([None] * extra))
 
 
-def _sn_stack(layers):
+def _sn_stack(layers, pair_out=None):
     """_SNStackFn over the n same-shaped spectrally normalised convolutions `layers`, or None when they do not qualify
-    (sigmas not precomputed by SpectralBatch.run, eval mode, other dtypes / devices): the caller then stacks `l.weight`."""
+    (sigmas not precomputed by SpectralBatch.run, eval mode, other dtypes / devices): the caller then stacks `l.weight`.
+    pair_out: a dict that receives the operand's bf16 pair as "w", written by the same launch."""
     sns, origs = [], []
     for l in layers:
         if not (isinstance(l, nn.Conv2d) and parametrize.is_parametrized(l, "weight")):
@@ -150,7 +155,8 @@ def _sn_stack(layers):
         return None
     if n > 1 and (origs[0].numel() % 4):
         return None
-    return _SNStackFn.apply(n, *[sn._sigma_pre for sn in sns], *[sn._u for sn in sns], *[sn._v for sn in sns], *origs)
+    return _SNStackFn.apply(n, *[sn._sigma_pre for sn in sns], *[sn._u for sn in sns], *[sn._v for sn in sns], *origs,
+                            *([pair_out] if pair_out is not None else []))
 
 
 def spectral_norm(module, name="weight", n_power_iterations=1, eps=1e-12):
@@ -634,8 +640,8 @@ class _StackedConvMfmaFn(torch.autograd.Function):
     while the weights are frozen (the split / transposed-split operands of W are built once per step)."""
 
     @staticmethod
-    def forward(ctx, k, stride, pad, rows, geom, wcache, out_pair, weight, bias, x, xh, xl, link=None, below=None):
-        """link / below: plain dicts shared with the layer above / below (None: no fusion across this boundary).  The backward of the
+    def forward(ctx, k, stride, pad, rows, geom, wcache, out_pair, weight, bias, x, xh, xl, link=None, below=None, wpair=None):
+        """wpair: the bf16 pair of `weight` where its producer wrote it (_SNStackFn), else it is split here.  link / below: plain dicts shared with the layer above / below (None: no fusion across this boundary).  The backward of the
         layer ABOVE may finish this layer's activation backward in its input-gradient epilogue (csrc/convgemm.hip EPI 2) and leave the
         result in link["stash"]; this layer's backward then starts from it (see _fuse_below)."""
         from . import convgemm as cg
@@ -645,7 +651,7 @@ class _StackedConvMfmaFn(torch.autograd.Function):
         f32 = x.shape[2] < 128 and _l1_mode() == "f32"       # the 32 -> 128 layer: exact-f32 products, forward and input gradient
         ops = wcache.get("ops") if wcache is not None else None
         if ops is None:
-            ops = {} if f32 else {"w": split_bf16(w)}
+            ops = {} if f32 else {"w": wpair if wpair is not None else split_bf16(w)}
             if wcache is not None:
                 wcache["ops"] = ops
         if f32:
@@ -732,13 +738,19 @@ class _StackedConvMfmaFn(torch.autograd.Function):
         dx = dw = db = None
         if fp32_dgrad and ctx.f32:
             if "wt32" not in ops:      # (n, Cout, k, C) -> (n, C, k*Cout) fp32: the input gradient's B operand, (tap, output channel) order
-                ops["wt32"] = w.view(n, N, k, C).permute(0, 3, 2, 1).reshape(n, C, k * N).contiguous()
+                if bind.weight_transpose_supported(N, C):      # one pass through LDS tiles (csrc/split.hip)
+                    ops["wt32"] = bind.weight_transpose(w, k, pair=False)
+                else:
+                    ops["wt32"] = w.view(n, N, k, C).permute(0, 3, 2, 1).reshape(n, C, k * N).contiguous()
             dx = cg.conv_dgrad_f32(gx, ops["wt32"], geom, k, stride, pad, xshape[1])      # exact-f32 implicit GEMM: no column operand, no col2im
         elif fp32_dgrad:
             dx = bind.col2im_kx1_stacked(torch.bmm(gx, w), geom, xshape, k, stride, pad)      # dcols (n, M, k*C) fp32
         elif ctx.needs_input_grad[9]:
             if "wt" not in ops:      # (n, Cout, k, C) -> (n, C, k*Cout): the dgrad GEMM's B operand, (tap, output channel) order
-                ops["wt"] = split_bf16(w.view(n, N, k, C).permute(0, 3, 2, 1).reshape(n, C, k * N).contiguous())
+                if bind.weight_transpose_supported(N, C):      # transposed and split in one pass (csrc/split.hip)
+                    ops["wt"] = bind.weight_transpose(w, k, pair=True)
+                else:
+                    ops["wt"] = split_bf16(w.view(n, N, k, C).permute(0, 3, 2, 1).reshape(n, C, k * N).contiguous())
             wth, wtl = ops["wt"]
             if _StackedConvMfmaFn._fuse_below(ctx, gh, gl, wth, wtl, geom, k, stride, pad, xshape[1], skip_w):
                 dx = _poison(gy.device).expand(xshape)      # nobody may read it: the layer below starts from below["stash"]
@@ -751,7 +763,7 @@ class _StackedConvMfmaFn(torch.autograd.Function):
                 dw = cg.conv_wgrad(gh, gl, xh, xl, geom, k, stride, pad).to(wdt)
             if want_db:
                 db = db32.to(bdt)
-        return (None, None, None, None, None, None, None, dw, db, dx, None, None, None, None)
+        return (None, None, None, None, None, None, None, dw, db, dx, None, None, None, None, None)
 
 
 _POISON = {}
@@ -804,15 +816,42 @@ class _StackedConvPostFn(torch.autograd.Function):
     """conv_post (C -> 1 channels, kernel (3,1), stride 1, padding 1) of all n period discriminators directly on the previous
     layer's stacked output x (n, rows, C) — csrc/convpost.hip: one streaming pass forward, one backward, instead of a
     (rows, 3C) im2col operand feeding a GEMV.  W (n, 1, 3C) in (tap, channel) order, bias (n, 1); Ms[i] valid rows =
-    whole sequences of Hs[i] positions.  Returns (n, rows, 1)."""
+    whole sequences of Hs[i] positions.  Returns (n, rows, 1).
+    below: the link dict of the _StackedConvMfmaFn layer that produced x (None: no fusion across this boundary): the backward may finish
+    that layer's activation backward in its own launch (vmasr_conv_post_bwd_gelu) and leave the result in below["stash"] (see _fuse_below)."""
 
     @staticmethod
-    def forward(ctx, Ms, Hs, W, bias, x):
+    def forward(ctx, Ms, Hs, W, bias, x, below=None):
         xc, w32, b32 = x.contiguous(), W.detach().float().contiguous(), bias.detach().float().contiguous()
         y = bind.conv_post_fwd(xc, w32, b32, Ms, Hs)
         ctx.save_for_backward(xc, w32)
         ctx.meta = (tuple(Ms), tuple(Hs), W.dtype, bias.dtype, tuple(bias.shape))
+        ctx.below = below
         return y
+
+    @staticmethod
+    def _fuse_below(ctx, xc, w32, gy, Ms, Hs, want_dw, want_db, skip_w):
+        """The input gradient of conv_post + the activation backward of the layer below in one launch, under the conditions of
+        _StackedConvMfmaFn._fuse_below: -> (dw, db) with the result left in below["stash"] / below["stash_db"] (the caller returns a
+        poisoned placeholder as dx), or None (nothing done)."""
+        b = ctx.below
+        if b is None or "pre" not in b or not knobs.get("VMASR_MPD_FUSE_GELU_BWD") or _lib.det_mode() or b["pre"].shape != xc.shape:
+            return None
+        want_dbcol = b["b_req"] and not skip_w
+        want_f32 = b["C"] < 128 and b["x_req"]
+        want_pair = (not want_f32 and b["x_req"]) or (b["w_req"] and not skip_w)
+        if not (want_f32 or want_pair):
+            return None
+        h = b.get("tap")      # the map must have no other consumer: cases (a) and (b) of _StackedConvMfmaFn._fuse_below
+        kw = {}
+        if h is not None and h.get("sgn") is not None and h.get("gtok") is not None and h["sgn"].shape == xc.shape:
+            kw = dict(sgn=h["sgn"], gtok=h["gtok"], scale=h["scale"], valid=h["valid"])
+            h["consumed"] = True
+        elif not _PHASE["scores_only"]:
+            return None
+        g32, pair, dbcol, dw, db = bind.conv_post_bwd_gelu(xc, w32, gy, b["pre"], Ms, Hs, want_pair, want_f32, want_dw, want_db, want_dbcol, **kw)
+        b["stash"], b["stash_db"] = (g32, pair), dbcol
+        return dw, db
 
     @staticmethod
     def backward(ctx, gy):
@@ -821,8 +860,12 @@ class _StackedConvPostFn(torch.autograd.Function):
         gy = gy.float().contiguous()
         skip_w = _PHASE["skip_weight_grads"]
         want_dx, want_dw, want_db = ctx.needs_input_grad[4], ctx.needs_input_grad[2] and not skip_w, ctx.needs_input_grad[3] and not skip_w
-        dx, dw, db = bind.conv_post_bwd(xc, w32, gy, Ms, Hs, want_dx, want_dw, want_db)
-        return (None, None, dw.to(wdt) if want_dw else None, db.view(bshape).to(bdt) if want_db else None, dx)
+        fused = _StackedConvPostFn._fuse_below(ctx, xc, w32, gy, Ms, Hs, want_dw, want_db, skip_w) if want_dx else None
+        if fused is not None:
+            (dw, db), dx = fused, _poison(gy.device).expand(xc.shape)      # nobody may read it: the layer below starts from below["stash"]
+        else:
+            dx, dw, db = bind.conv_post_bwd(xc, w32, gy, Ms, Hs, want_dx, want_dw, want_db)
+        return (None, None, dw.to(wdt) if want_dw else None, db.view(bshape).to(bdt) if want_db else None, dx, None)
 
 
 class _UnstackRowsFn(torch.autograd.Function):
@@ -1080,6 +1123,21 @@ class MultiPeriodDiscriminator(nn.Module):
             P = [c.shape[1] for c in cur]
             H1 = [(c.shape[2] + 2 * pad - k) // stride + 1 for c in cur]
             Ms = [B * p * h for p, h in zip(P, H1)]
+            act = li < len(discs[0].layers)
+            # from the second layer on the inputs are the slots of the previous layer's stacked output: hand that tensor over
+            # (slot i = B*p_i sequences of H_i positions) so that its gradient comes back stacked, in one launch
+            sgeom, src = None, cur
+            pair, next_pair = next_pair, None     # the bf16 (hi, lo) pair of stacks[-1], if the previous layer's epilogue wrote it
+            prev_link, this_link = this_link, None   # set by an MFMA layer: the layer above may finish its activation backward
+            if stacks and stacks[-1].dtype == cdt and knobs.get("VMASR_STACK_INPUT"):
+                sgeom, src = tuple((B * p, c.shape[2]) for c, p in zip(cur, P)), (stacks[-1],)
+            rows = _round_up(max(Ms), 256)
+            Cin = cur[0].shape[3]
+            path = _layer_path(li, act, cdt, stacks[-1].dtype if stacks else None, sgeom is not None, k, stride, pad, Cin,
+                               layers[0].out_channels, n, max(Ms), max(B * p * c.shape[2] for c, p in zip(cur, P)))
+            wcache = wpair = None
+            if path == "mfma" and self._frozen is not None:
+                wcache = self._frozen.setdefault(("mfma_ops", li), {})
             W = None
             if knobs.get("VMASR_SN_STACK"):
                 # normalisation, stack and (tap, c) permutation of the layer's n weights in one launch; while the trainer
@@ -1087,7 +1145,11 @@ class MultiPeriodDiscriminator(nn.Module):
                 key = (li, bool(detach_weights))
                 W = self._frozen.get(key) if self._frozen is not None else None
                 if W is None:
-                    W = _sn_stack(layers)
+                    # an MFMA layer on bf16 pairs that has no weight operand yet: the same launch writes the pair of W
+                    got = {} if (path == "mfma" and not (Cin < 128 and _l1_mode() == "f32")
+                                 and (wcache is None or "ops" not in wcache)) else None
+                    W = _sn_stack(layers, got)
+                    wpair = got.get("w") if got is not None else None
                     if W is not None and detach_weights:
                         W = W.detach()
                     if W is not None and self._frozen is not None:
@@ -1099,30 +1161,16 @@ class MultiPeriodDiscriminator(nn.Module):
                 # (n, Cout, k, Cin) -> (n, Cout, k*Cin): (tap, c) column order, gathered by the stack's own copy
                 W = torch.stack([w.squeeze(3).transpose(1, 2) for w, _ in ws])
                 W = W.reshape(n, W.shape[1], -1)
-            act = li < len(discs[0].layers)
             bstack = torch.stack([b for _, b in ws])
-            # from the second layer on the inputs are the slots of the previous layer's stacked output: hand that tensor over
-            # (slot i = B*p_i sequences of H_i positions) so that its gradient comes back stacked, in one launch
-            sgeom, src = None, cur
-            pair, next_pair = next_pair, None     # the bf16 (hi, lo) pair of stacks[-1], if the previous layer's epilogue wrote it
-            prev_link, this_link = this_link, None   # set by an MFMA layer: the layer above may finish its activation backward
-            if stacks and stacks[-1].dtype == cdt and knobs.get("VMASR_STACK_INPUT"):
-                sgeom, src = tuple((B * p, c.shape[2]) for c, p in zip(cur, P)), (stacks[-1],)
-            rows = _round_up(max(Ms), 256)
-            path = _layer_path(li, act, cdt, stacks[-1].dtype if stacks else None, sgeom is not None, k, stride, pad, cur[0].shape[3],
-                               W.shape[1], n, max(Ms), max(B * p * c.shape[2] for c, p in zip(cur, P)))
             if path == "post":      # straight on the previous layer's stacked maps (no column operand)
-                y = _StackedConvPostFn.apply(tuple(valid[-1]), tuple(c.shape[2] for c in cur), W, bstack, stacks[-1])
+                y = _StackedConvPostFn.apply(tuple(valid[-1]), tuple(c.shape[2] for c in cur), W, bstack, stacks[-1], prev_link)
             elif path == "first":   # straight from the folded signals (no 5-column operand / K = 5 GEMM)
                 y = _StackedConvFirstFn.apply(rows, W, bstack, *cur)
             elif path == "mfma":    # one implicit-GEMM launch each way; the epilogue leaves the bf16 pair of its activation for the next layer
-                wcache = None
-                if self._frozen is not None:
-                    wcache = self._frozen.setdefault(("mfma_ops", li), {})
                 out_pair = []
                 xh, xl = pair if pair is not None else (None, None)
                 link = {}
-                y = _StackedConvMfmaFn.apply(k, stride, pad, rows, sgeom, wcache, out_pair, W, bstack, src[0], xh, xl, link, prev_link)
+                y = _StackedConvMfmaFn.apply(k, stride, pad, rows, sgeom, wcache, out_pair, W, bstack, src[0], xh, xl, link, prev_link, wpair)
                 next_pair, this_link = out_pair[0], link
             elif path == "split":
                 y = _StackedConvSplitFn.apply(k, stride, pad, rows, act, sgeom, W, bstack, *src)

@@ -209,6 +209,22 @@ def conv_post_bwd(x, w, gy, Ms, Hs, want_dx, want_dw, want_db):
     return dx, dw, db
 
 
+def conv_post_bwd_gelu(x, w, gy, pre, Ms, Hs, want_pair, want_f32, want_dw, want_db, want_dbcol, sgn=None, gtok=None, valid=None, scale=None):
+    """conv_post_bwd with the activation backward of the layer below in it (csrc/convpost.hip): g = (dx + gtok * scale[s] * sgn) * GELU'(pre),
+    the sign term (sgn int8, x's shape; gtok one fp32 element) on the rows < valid[s].  -> (g fp32 or None, (gh, gl) bf16 pair or None,
+    dbcol (n, C) column sums of g or None, dw (n, 1, 3C) or None, db (n,) or None); dx itself is never written."""
+    n, rows, C = x.shape
+    ms, hs = (ctypes.c_int64 * n)(*Ms), (ctypes.c_int32 * n)(*Hs)
+    v, sc = _valid_scale(valid, scale) if sgn is not None else (None, None)
+    g32 = torch.empty_like(x) if want_f32 else None
+    gh = _new(x, x.shape, _BF16) if want_pair else None
+    gl = _new(x, x.shape, _BF16) if want_pair else None
+    dw, db, dbcol = _lib.zeros_f32(x.device, (n, 1, 3 * C) if want_dw else None, (n,) if want_db else None, (n, C) if want_dbcol else None)
+    _call(_lib.lib().vmasr_conv_post_bwd_gelu, x if want_dw else None, w, gy, pre, sgn, gtok if sgn is not None else None, v, sc, gh, gl, g32,
+          dw, db, dbcol, ms, hs, n, rows, C, 3)
+    return g32, ((gh, gl) if want_pair else None), dbcol, dw, db
+
+
 def conv_mfma_supported_launch(Cin, Cout, k, stride, n, rows):
     return bool(_lib.lib().vmasr_conv_mfma_supported_launch(int(Cin), int(Cout), int(k), int(stride), int(n), int(rows)))
 
@@ -239,11 +255,31 @@ def masked_l1_bwd(sgn, g, valid, scale, add=None, tap=False):
     return out
 
 
-def sn_stack_fwd(ws, sig):
-    """out[s] = permute(ws[s] / sig[s]): n weights (N, Cin, k, 1) -> one (n, N, k*Cin) operand in (tap, channel) column order."""
+def sn_stack_fwd(ws, sig, want_pair=False):
+    """out[s] = permute(ws[s] / sig[s]): n weights (N, Cin, k, 1) -> one (n, N, k*Cin) operand in (tap, channel) column order.
+    want_pair: -> (out, (hi, lo)), its bf16 pair (split_bf16's) written in the same pass."""
     n, (N, Cin, k) = len(ws), ws[0].shape[:3]
     out = _new(ws[0], (n, N, k * Cin), _F32)
-    _call(_lib.lib().vmasr_sn_stack_fwd, _ptr_array(ws), _ptr_array(sig), n, out, N, Cin, k)
+    hi, lo = (_new(out, out.shape, _BF16), _new(out, out.shape, _BF16)) if want_pair else (None, None)
+    _call(_lib.lib().vmasr_sn_stack_fwd, _ptr_array(ws), _ptr_array(sig), n, out, hi, lo, N, Cin, k)
+    return (out, (hi, lo)) if want_pair else out
+
+
+def weight_transpose_supported(N, Cin):
+    return Cin % 4 == 0 and N % 8 == 0
+
+
+def weight_transpose(w, k, pair):
+    """w (n, N, k*Cin) fp32, (tap, channel) columns -> the input gradient's operand (n, Cin, k*N) in (tap, output channel) order, one pass
+    (csrc/split.hip): its bf16 pair (hi, lo) if pair, else fp32.  == split_bf16 of / the permute(0, 3, 2, 1) copy of w.view(n, N, k, Cin)."""
+    n, N, K = w.shape
+    Cin = K // k
+    if pair:
+        hi, lo = _new(w, (n, Cin, k * N), _BF16), _new(w, (n, Cin, k * N), _BF16)
+        _call(_lib.lib().vmasr_weight_transpose, w, hi, lo, None, n, N, Cin, k)
+        return hi, lo
+    out = _new(w, (n, Cin, k * N), _F32)
+    _call(_lib.lib().vmasr_weight_transpose, w, None, None, out, n, N, Cin, k)
     return out
 
 
