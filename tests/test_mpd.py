@@ -649,6 +649,7 @@ def test_feature_tap_gradient_equals_loss_backward_plus_autograd_sum(n, rows, N,
     bit-equal (one fused multiply-add per element instead of a multiply and an add: equal to 1 ulp) — and a tap nobody feeds
     passes the gradient through."""
     from vm_asr_amd.discriminator import _FeatTapFn, _MaskedL1Fn
+    from vm_asr_amd.mpd_link import _Tap
     torch.manual_seed(n + N)
     real = torch.randn(n, rows, N, device="cuda")
     x = torch.randn(n, rows, N, device="cuda")
@@ -659,16 +660,16 @@ def test_feature_tap_gradient_equals_loss_backward_plus_autograd_sum(n, rows, N,
         xi = x.clone().requires_grad_()
         y = xi * 2.0
         if tapped:
-            holder = {}
-            y, tok = _FeatTapFn.apply(y, holder)
-            fm = _MaskedL1Fn.apply(real, y.detach(), valid, scale, tok, holder)
+            tap = _Tap()
+            y, tok = _FeatTapFn.apply(y, tap)
+            fm = _MaskedL1Fn.apply(real, y.detach(), valid, scale, tok, tap)
         else:
             fm = _MaskedL1Fn.apply(real, y, valid, scale, None, None)
         ((y * w).sum() + 3.0 * fm).backward()
         grads.append(xi.grad.clone())
     assert torch.allclose(grads[0], grads[1], rtol=2e-7, atol=1e-9)
     xi = x.clone().requires_grad_()
-    y, tok = _FeatTapFn.apply(xi * 2.0, {})
+    y, tok = _FeatTapFn.apply(xi * 2.0, _Tap())
     (y * w).sum().backward()
     assert torch.equal(xi.grad, 2.0 * w)
 
