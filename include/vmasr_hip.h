@@ -677,6 +677,29 @@ int vmasr_stft_loss_fwd(const float *re_x, const float *im_x, const float *re_y,
 int vmasr_stft_loss_bwd(const float *re_x, const float *im_x, const float *re_y, const float *im_y, int64_t n, const float *fin,
                         const float *g_sc, const float *g_ml, float *d_re, float *d_im, vmasr_stream_t stream);
 
+/* ---- strided grouped 1-D convolution of the multi-scale discriminator (vm_asr_amd/csrc/gconv1d.hip; model/discriminator.py:189-238) ----
+ *   y[b, g Co + o, t] = bias[g Co + o] + sum_{c < Ci} sum_{j < k} w[g Co + o, c, j] x[b, g Ci + c, t stride + j - pad],   x = 0 outside [0, L)
+ * x (B, Cin, L), w (Cout, Cin / groups, k), y (B, Cout, T) with T = (L + 2 pad - k) / stride + 1: fp32, contiguous, channel-first.
+ * Exact-fp32 products on the matrix cores (v_mfma_f32_16x16x4_f32).  vmasr_gconv1d_supported: k 41, stride 4, groups dividing Cin and
+ * Cout (every per-group channel pair, 1 included); _supported_launch adds what a launch needs: 0 <= pad < k, 1 <= B <= 65535,
+ * k - 2 pad <= L <= 2^28, B * ceil(T / 64) <= 2^30 (the weight gradient's 32-bit count of its K units).
+ * The three launchers check exactly that predicate; anything else is VMASR_EINVAL with nothing launched, as is
+ * a null pointer.
+ * fwd  : bias may be NULL.  act != 0: pre = the convolution + bias (kept for the backward), y = GELU(pre) (exact erf); act == 0: y alone.
+ * dgrad: dx (B, Cin, L) from gy (B, Cout, T); pre != NULL: gy is first multiplied by GELU'(pre).  Every element of dx is written.
+ * wgrad: dw (Cout, Ci, k) and / or db (Cout) (either may be NULL) from x and gy (same GELU' rule).  ws: scratch of
+ *        vmasr_gconv1d_wgrad_workspace() bytes (0 for a refused shape) holding split-K partials that a second launch adds in a fixed
+ *        order: no float atomics, bit-identical from call to call. */
+int vmasr_gconv1d_supported(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride);
+int vmasr_gconv1d_supported_launch(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+size_t vmasr_gconv1d_wgrad_workspace(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+int vmasr_gconv1d_fwd(const float *x, const float *w, const float *bias, float *y, float *pre, int32_t B, int32_t Cin, int32_t Cout,
+                      int32_t groups, int64_t L, int32_t k, int32_t stride, int32_t pad, int32_t act, vmasr_stream_t stream);
+int vmasr_gconv1d_dgrad(const float *gy, const float *pre, const float *w, float *dx, int32_t B, int32_t Cin, int32_t Cout, int32_t groups,
+                        int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
+int vmasr_gconv1d_wgrad(const float *x, const float *gy, const float *pre, float *dw, float *db, void *ws, size_t ws_bytes, int32_t B,
+                        int32_t Cin, int32_t Cout, int32_t groups, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) ---------------------
  * When enabled, every kernel launch of this library is bracketed by two hipEvents
  * recorded on the stream the kernel is launched on; vmasr_prof_collect() waits for the
@@ -749,6 +772,10 @@ enum {
     VMASR_K_METRICS,            /* SNR / LSD / LSD-HF / LSD-LF of a batch: packed out/tgt FFT per frame + finish (csrc/metrics.hip) */
     VMASR_K_RESAMPLE_DESIGN,    /* resampling filter designed on the device: taps + partial sums, normalise (csrc/resample.hip) */
     VMASR_K_DEGRADE_BATCH,      /* a batch degraded at per-clip rates: down pass, up pass + align (csrc/resample.hip) */
+    VMASR_K_GCONV1D_FWD,        /* scale discriminator: strided grouped 1-D convolution + bias + GELU, exact-f32 MFMA (csrc/gconv1d.hip) */
+    VMASR_K_GCONV1D_DGRAD,      /* its input gradient by residue classes of the stride, GELU' of the incoming gradient on the fly */
+    VMASR_K_GCONV1D_WGRAD,      /* its weight / bias gradient: split-K partials into a workspace */
+    VMASR_K_GCONV1D_WGRAD_REDUCE, /* the ordered sum of those partials (no float atomics) */
     VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };

@@ -76,6 +76,13 @@ def parse_option(argv=None):
     return args, config
 
 
+def use_graphs(args, config):
+    """Whether training replays HIP graphs: the default, except under --no-graphs, with gradient accumulation, and when the multi-scale
+    discriminator is listed (its step is eager only: Trainer.enable_graphs raises; the optimisers are then built non-capturable too)."""
+    adv = config.TRAIN.ADVERSARIAL
+    return not args.no_graphs and config.TRAIN.ACCUMULATION_STEPS == 1 and not (adv.ENABLE and "msd" in adv.DISCRIMINATORS)
+
+
 def main(args, config):
     import vm_asr_amd
     from vm_asr_amd.trainer import (CosineWarmupScheduler, SyntheticVCTK, Trainer, _Logger, build_optimizer, default_metric_ftns,
@@ -118,7 +125,7 @@ def main(args, config):
         print({k: round(v, 4) if isinstance(v, float) else v for k, v in res.items()})
         return
     gan = config.TRAIN.ADVERSARIAL.ENABLE
-    graphs = not args.no_graphs and config.TRAIN.ACCUMULATION_STEPS == 1
+    graphs = use_graphs(args, config)
     val_loader = None
     if args.data_path:
         from vm_asr_amd.data import get_loader
@@ -140,6 +147,8 @@ def main(args, config):
                                       config.TRAIN.MIN_LR, config.TRAIN.LR_SCHEDULER.WARMUP_PREFIX) for k, o in opts.items()}
     tr = Trainer(models, metrics, opts, config, device, loader, val_loader, sched, amp=config.AMP_ENABLE, gan=gan, logger=log,
                  step_metrics=args.step_metrics)
+    if gan and "msd" in config.TRAIN.ADVERSARIAL.DISCRIMINATORS and not args.no_graphs:
+        log.info("DISCRIMINATORS lists 'msd': the step runs eagerly (no HIP graphs), as under --no-graphs")
     if graphs:
         first = next(iter(loader))
         tr.enable_graphs(tr._to_dev(first))

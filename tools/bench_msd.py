@@ -1,0 +1,139 @@
+"""Times the multi-scale discriminator's grouped convolutions, `hip` (csrc/gconv1d.hip) against `torch` (F.conv1d), and the eager
+["mpd", "msd"] train step.  One process, one device.  Every figure compares the two routes in the same call, ALTERNATING them: after
+warm-up calls of both, `--rounds` rounds of (hip window, torch window); a window is n back-to-back calls between two HIP events, n
+chosen per route so that a window lasts about `--window-ms`; the figure of a window is its time / n.  Reported per route: the median,
+the minimum and the maximum of the windows (the spread: a difference inside it is not one).  profiles/msd.md holds the output.
+
+    python tools/bench_msd.py [--batch 4] [--samples 122640] [--rounds 7] [--window-ms 100] [--step] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+K, S, PAD = 41, 4, 20
+
+
+def _window(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def compare(fns, rounds, window_ms, warmup=3, max_calls=4000):
+    """fns: {route: callable}.  -> {route: {"ms": median, "min": ..., "max": ..., "calls": n per window}} from alternated windows."""
+    n = {}
+    for k, fn in fns.items():
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        n[k] = max(1, min(max_calls, int(window_ms / max(_window(fn, 3), 1e-4))))
+    ms = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            ms[k].append(_window(fn, n[k]))
+    return {k: {"ms": statistics.median(v), "min": min(v), "max": max(v), "calls": n[k]} for k, v in ms.items()}
+
+
+def layer_rows(batch, samples, rounds, window_ms, hidden=128):
+    from vm_asr_amd import msd_ops
+    h = hidden
+    layers = [(h, h, 4), (h, 2 * h, 16), (2 * h, 4 * h, 16), (4 * h, 8 * h, 16), (8 * h, 8 * h, 16)]
+    L, rows = samples, []
+    g_in = torch.ops.aten.gelu_backward
+    for li, (ci, co, g) in enumerate(layers, start=1):
+        T = (L + 2 * PAD - K) // S + 1
+        x = torch.randn(batch, ci, L, device="cuda")
+        w = torch.randn(co, ci // g, K, device="cuda") / (ci // g * K) ** 0.5
+        b = torch.randn(co, device="cuda")
+        gy = torch.randn(batch, co, T, device="cuda")
+        y, pre = msd_ops.gconv1d_fwd(x, w, b, g, S, PAD, True)
+        gflop = 2.0 * batch * co * T * (ci // g) * K / 1e9
+        row = {"layer": f"convs.{li}", "Cin": ci, "Cout": co, "groups": g, "L": L, "T": T, "gflop": round(gflop, 2)}
+        ops = {
+            "fwd": {"hip": lambda: msd_ops.gconv1d_fwd(x, w, b, g, S, PAD, True), "torch": lambda: F.gelu(F.conv1d(x, w, b, S, PAD, 1, g))},
+            "dgrad": {"hip": lambda: msd_ops.gconv1d_dgrad(gy, pre, w, x.shape, g, S, PAD),
+                      "torch": lambda: torch.ops.aten.convolution_backward(g_in(gy, pre), x, w, [co], [S], [PAD], [1], False, [0], g,
+                                                                           [True, False, False])},
+            "wgrad": {"hip": lambda: msd_ops.gconv1d_wgrad(x, gy, pre, w.shape, g, S, PAD),
+                      "torch": lambda: torch.ops.aten.convolution_backward(g_in(gy, pre), x, w, [co], [S], [PAD], [1], False, [0], g,
+                                                                           [False, True, True])},
+        }
+        for op, fns in ops.items():
+            for route, r in compare(fns, rounds, window_ms).items():
+                row[f"{route}_{op}_ms"], row[f"{route}_{op}_min"], row[f"{route}_{op}_max"] = r["ms"], r["min"], r["max"]
+                row[f"{route}_{op}_calls"] = r["calls"]
+        rows.append(row)
+        L = T
+    return rows
+
+
+def step_ms(batch, samples, rounds, steps=4):
+    """One trainer; VMASR_MSD_CONV is read at every call, so the two routes alternate in windows of `steps` steps on the same state."""
+    from vm_asr_amd import get_model
+    from vm_asr_amd.config import get_default_config, update_config
+    from vm_asr_amd.trainer import SyntheticVCTK, Trainer, build_optimizer
+    c = get_default_config()           # bench.py's vm_asr_48k_MPD workload with the MSD listed beside the MPD
+    c.MODEL.NAME = "DualStreamInteractiveMambaUNet"
+    c.TRAIN.LOW_FREQ_REPLACEMENT = True
+    c.DATA.TARGET_SR = 48000
+    c.DATA.LPF.MULTIFILTER = True
+    c.TRAIN.ADVERSARIAL.ENABLE = True
+    c.TRAIN.ADVERSARIAL.DISCRIMINATORS = ["mpd", "msd"]
+    c.DATA.BATCH_SIZE = batch
+    config = update_config(c)
+    torch.manual_seed(config.SEED)
+    models = get_model(config)
+    dev = torch.device("cuda:0")
+    opts = {"generator": build_optimizer(config, models["generator"]),
+            "discriminator": build_optimizer(config, [models["mpd"], models["msd"]])}
+    tr = Trainer(models, [], opts, config, dev, None, None, {}, amp=True, gan=True, len_epoch=0, dp_mode="flat")
+    for m in tr.models.values():
+        m.train()
+    ds = SyntheticVCTK(config, length=batch, sr_in=16000, seed=123)
+    inp, tgt, hc = next(iter(torch.utils.data.DataLoader(ds, batch_size=batch, shuffle=False)))[:3]
+    wave_in, wave, hf = inp.to(dev), tgt.to(dev), hc.to(dev)
+    ms = {"hip": [], "torch": []}
+    for mode in ms:                    # warm-up of both routes
+        os.environ["VMASR_MSD_CONV"] = mode
+        for _ in range(3):
+            tr.train_step(wave_in, wave, hf)
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for mode in ms:
+            os.environ["VMASR_MSD_CONV"] = mode
+            ms[mode].append(_window(lambda: tr.train_step(wave_in, wave, hf), steps))
+    os.environ.pop("VMASR_MSD_CONV")
+    return {k: {"ms": statistics.median(v), "min": min(v), "max": max(v), "calls": steps} for k, v in ms.items()}
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--samples", type=int, default=122640)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--window-ms", type=float, default=100.0)
+    ap.add_argument("--step", action="store_true", help="also time the eager ['mpd', 'msd'] train step, hip and torch alternated")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = {"device": torch.cuda.get_device_name(0), "batch": a.batch, "samples": a.samples, "rounds": a.rounds, "window_ms": a.window_ms,
+           "layers": layer_rows(a.batch, a.samples, a.rounds, a.window_ms)}
+    for r in res["layers"]:
+        print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+    if a.step:
+        res["step"] = step_ms(a.batch, a.samples, a.rounds)
+        print(json.dumps({"step": {k: {n: round(x, 2) for n, x in v.items()} for k, v in res["step"].items()}}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)

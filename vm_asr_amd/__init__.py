@@ -14,7 +14,7 @@ from . import hip_env  # noqa: F401,E402  (runtime settings, before anything tou
 
 def get_model(config):
     """Build the models a config asks for — same contract as the reference's
-    model/__init__.py:8-66 (`{"generator": ..., "mpd": ...}`)."""
+    model/__init__.py:8-66 (`{"generator": ..., "mpd": ..., "msd": ...}`; the MSD at the reference's fixed width, hidden 128)."""
     from .discriminator import MultiPeriodDiscriminator
     from .model import DualStreamInteractiveMambaUNet
 
@@ -38,5 +38,6 @@ def get_model(config):
         if "mpd" in config.TRAIN.ADVERSARIAL.DISCRIMINATORS:
             models["mpd"] = MultiPeriodDiscriminator(hidden=config.TRAIN.ADVERSARIAL.MPD_HIDDEN)
         if "msd" in config.TRAIN.ADVERSARIAL.DISCRIMINATORS:
-            raise NotImplementedError("MSD is not enabled by any shipped yaml and is not built")
+            from .msd import MultiScaleDiscriminator
+            models["msd"] = MultiScaleDiscriminator()
     return models

@@ -203,6 +203,12 @@ SYMBOLS = {
     "vmasr_istft_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_metrics_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_metrics": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "vmasr_gconv1d_supported": (ctypes.c_int, [c_i32] * 5),
+    "vmasr_gconv1d_supported_launch": (ctypes.c_int, [c_i32] * 7 + [c_i64]),
+    "vmasr_gconv1d_wgrad_workspace": (c_sz, [c_i32] * 7 + [c_i64]),
+    "vmasr_gconv1d_fwd": (ctypes.c_int, [c_vp] * 5 + [c_i32] * 4 + [c_i64] + [c_i32] * 4 + [c_vp]),
+    "vmasr_gconv1d_dgrad": (ctypes.c_int, [c_vp] * 4 + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
+    "vmasr_gconv1d_wgrad": (ctypes.c_int, [c_vp] * 6 + [c_sz] + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
     "vmasr_resample_poly": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_resample_design_workspace": (c_sz, [c_i32]),
     "vmasr_resample_design": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
@@ -328,7 +334,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 66
+K_COUNT = 70
 
 
 def zeros_f32(device, *shapes):

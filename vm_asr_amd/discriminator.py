@@ -4,7 +4,7 @@ Re-statement of model/discriminator.py:21-147 (HiFi-GAN style, periods 2,3,5,7,1
 -> 41.09 M parameters).  The reference's inverted ternary (`weight_norm if use_spectral_norm
 else spectral_norm`, :37) means the default `use_spectral_norm=False` yields SPECTRAL norm;
 that is reproduced so state_dicts (parametrizations.weight.original + power-iteration
-buffers) stay compatible.  MSD (:174-337) is not enabled by any yaml and is not built.
+buffers) stay compatible.  The multi-scale discriminator (:174-337) is vm_asr_amd/msd.py.
 
 How it runs on the GPU (MIOpen has only `naive_conv_*` fallbacks for these (k,1) convolutions):
 

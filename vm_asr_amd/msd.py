@@ -1,0 +1,167 @@
+"""Multi-scale discriminator: the second adversary the reference can build from TRAIN.ADVERSARIAL.DISCRIMINATORS.
+
+Re-statement of model/discriminator.py:174-313 (HiFi-GAN style: three ScaleDiscriminators, the second and third behind a cumulative
+AvgPool1d(4, 2, padding=2); hidden 128).  As for the MPD, the reference's inverted ternary (`weight_norm if use_spectral_norm else
+spectral_norm`, :177) means the default `use_spectral_norm=False` yields SPECTRAL norm; that is reproduced, so state_dicts
+(`discriminators.{i}.convs.{j}.parametrizations.weight.original`, `....parametrizations.weight.0._u/_v`, `....bias`,
+`discriminators.{i}.conv_post....`) load strict=True in both directions.
+
+How it runs:
+
+  * CPU tensors: plain torch (F.conv1d + F.gelu), like the MPD.
+  * GPU: the five strided grouped convolutions (k 41, stride 4, pad 20, groups 4 / 16) run on csrc/gconv1d.hip — exact-fp32 MFMA
+    forward with bias + GELU in the epilogue, input gradient by stride residue classes, weight gradient as split-K partials with an
+    ordered sum (bit-identical from run to run).  The three dense layers (1 -> h k 15, 8h -> 8h k 5, 8h -> 1 k 3) and the pools are
+    torch operators.  VMASR_MSD_CONV=torch routes the grouped layers through F.conv1d too (A/B measurements; and what
+    discriminator.plain_torch_ops selects: the HIP functions are differentiable once).
+  * The module computes in fp32 with autocast disabled, so amp_scope="step" leaves the MSD in fp32.
+  * Spectral norm follows the reference's schedule exactly: one power iteration per training forward of a ScaleDiscriminator, the
+    weight normalised anew in every pass (the layers read their parametrization directly, so an enclosing
+    torch.nn.utils.parametrize.cached() — the MPD's once-per-step weights — does not freeze them).
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.nn.utils import parametrize
+from torch.nn.utils.parametrizations import weight_norm
+
+from . import knobs, msd_ops as bind
+from .discriminator import _PLAIN_OPS, _SpectralNorm, spectral_norm
+
+__all__ = ["ScaleDiscriminator", "MultiScaleDiscriminator", "grouped_conv1d"]
+
+
+class _GConv1dFn(torch.autograd.Function):
+    """y = [GELU](conv1d(x, w, bias, stride, pad, groups)) on the HIP kernels; saves x, w and the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, groups, stride, pad, act):
+        x, w = x.contiguous(), w.contiguous()
+        y, pre = bind.gconv1d_fwd(x, w, None if bias is None else bias.contiguous(), groups, stride, pad, act)
+        ctx.save_for_backward(x, w, pre)
+        ctx.geom = (groups, stride, pad, bias is not None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w, pre = ctx.saved_tensors
+        groups, stride, pad, has_bias = ctx.geom
+        gy = gy.contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        dx = bind.gconv1d_dgrad(gy, pre, w, x.shape, groups, stride, pad) if need_x else None
+        dw, db = bind.gconv1d_wgrad(x, gy, pre, w.shape, groups, stride, pad, need_w, need_b)
+        return dx, dw, db, None, None, None, None
+
+
+def _hip_ok(x, w, groups, stride, pad):
+    if not x.is_cuda or _PLAIN_OPS[0] or knobs.get("VMASR_MSD_CONV") != "hip":
+        return False
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or x.dim() != 3 or w.dim() != 3:
+        return False
+    if x.shape[1] % max(groups, 1) or w.shape[0] % max(groups, 1) or w.shape[1] * groups != x.shape[1]:
+        return False
+    return bind.gconv1d_supported_launch(x.shape[1], w.shape[0], groups, w.shape[2], stride, pad, x.shape[0], x.shape[2])
+
+
+def grouped_conv1d(x, w, bias, groups, stride, pad, act):
+    """[GELU](F.conv1d(x, w, bias, stride, pad, 1, groups)): the HIP kernels where vmasr_gconv1d_supported_launch accepts the call
+    (fp32 on the GPU, VMASR_MSD_CONV=hip), torch's operators otherwise."""
+    if _hip_ok(x, w, groups, stride, pad):
+        return _GConv1dFn.apply(x, w, bias, groups, stride, pad, act)
+    y = F.conv1d(x, w, bias, stride, pad, 1, groups)
+    return F.gelu(y) if act else y
+
+
+def _weight(layer):
+    """The layer's (normalised) weight, evaluated now: one power iteration in training mode, as every reference forward does."""
+    if parametrize.is_parametrized(layer, "weight"):
+        return layer.parametrizations.weight()
+    return layer.weight
+
+
+class ScaleDiscriminator(nn.Module):
+    def __init__(self, use_spectral_norm=False, hidden=128):
+        super().__init__()
+        norm = weight_norm if use_spectral_norm else spectral_norm  # sic
+        h = hidden
+        self.convs = nn.ModuleList([
+            norm(nn.Conv1d(1, h, 15, 1, padding=7)),
+            norm(nn.Conv1d(h, h, 41, 4, groups=4, padding=20)),
+            norm(nn.Conv1d(h, h * 2, 41, 4, groups=16, padding=20)),
+            norm(nn.Conv1d(h * 2, h * 4, 41, 4, groups=16, padding=20)),
+            norm(nn.Conv1d(h * 4, h * 8, 41, 4, groups=16, padding=20)),
+            norm(nn.Conv1d(h * 8, h * 8, 41, 4, groups=16, padding=20)),
+            norm(nn.Conv1d(h * 8, h * 8, 5, 1, padding=2)),
+        ])
+        self.conv_post = norm(nn.Conv1d(h * 8, 1, 3, 1, padding=1))
+
+    def forward(self, x, detach_weights=False):
+        """-> (score (B, T'), the eight feature maps).  `detach_weights`: the weights as constants — the generator's pass through
+        the discriminator, where no discriminator gradient is wanted."""
+        fmap = []
+        with torch.autocast(device_type=x.device.type, enabled=False):
+            if x.dtype in (torch.float16, torch.bfloat16):
+                x = x.float()
+            for layer in list(self.convs) + [self.conv_post]:
+                w, b = _weight(layer), layer.bias
+                if detach_weights:
+                    w, b = w.detach(), b.detach()
+                act = layer is not self.conv_post
+                if layer.groups > 1:
+                    x = grouped_conv1d(x, w, b, layer.groups, layer.stride[0], layer.padding[0], act)
+                else:
+                    x = F.conv1d(x, w, b, layer.stride, layer.padding)
+                    if act:
+                        x = F.gelu(x)
+                fmap.append(x)
+        return torch.flatten(x, 1, -1), fmap
+
+
+class MultiScaleDiscriminator(nn.Module):
+    def __init__(self, hidden=128):
+        super().__init__()
+        self.discriminators = nn.ModuleList([ScaleDiscriminator(hidden=hidden) for _ in range(3)])
+        self.meanpools = nn.ModuleList([nn.AvgPool1d(4, 2, padding=2), nn.AvgPool1d(4, 2, padding=2)])
+
+    def _scales(self, x):
+        """x at the three scales: itself, pooled once, pooled twice."""
+        xs = [x]
+        for pool in self.meanpools:
+            xs.append(pool(xs[-1]))
+        return xs
+
+    def forward(self, y, y_hat):
+        """The reference's call: every scale on the real, then on the generated signal (two power iterations per weight in
+        training mode).  y_hat None: zeros in the generated lists."""
+        y_real, y_gen, fmap_real, fmap_gen = [], [], [], []
+        ys = self._scales(y)
+        hs = self._scales(y_hat) if y_hat is not None else [None] * len(ys)
+        for disc, a, b in zip(self.discriminators, ys, hs):
+            r, fr = disc(a)
+            y_real.append(r)
+            fmap_real.append(fr)
+            if b is not None:
+                g, fg = disc(b)
+                y_gen.append(g)
+                fmap_gen.append(fg)
+            else:
+                y_gen.append(0)
+                fmap_gen.append(0)
+        return y_real, y_gen, fmap_real, fmap_gen
+
+    def forward_single(self, x, detach_weights=False):
+        """Scores and feature maps of ONE signal batch (the generator's pass: detach_weights=True uses the weights as constants)."""
+        res = [d(a, detach_weights) for d, a in zip(self.discriminators, self._scales(x))]
+        return [r[0] for r in res], [r[1] for r in res]
+
+    def forward_pair(self, y, y_hat):
+        """Same results as forward(y, y_hat) from ONE pass over the stacked batch [y; y_hat] (same weights, identical per-sample
+        arithmetic; ONE power iteration per weight instead of two)."""
+        n = y.shape[0]
+        scores, feats = self.forward_single(torch.cat((y, y_hat), dim=0))
+        return ([s[:n] for s in scores], [s[n:] for s in scores],
+                [[t[:n] for t in f] for f in feats], [[t[n:] for t in f] for f in feats])
+
+    def spectral_norms(self):
+        return [m for m in self.modules() if isinstance(m, _SpectralNorm)]

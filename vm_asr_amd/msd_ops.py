@@ -1,0 +1,57 @@
+"""The scale discriminator's HIP entry points (include/vmasr_hip.h, csrc/gconv1d.hip), one Python function each — the companion of
+mpd_ops.py.
+
+Every function takes tensors and plain numbers, allocates its outputs and launches through _lib.call.  No autograd and no switches here:
+vm_asr_amd/msd.py decides what runs.  Layout: channel-first fp32, x (B, Cin, L), w (Cout, Cin / groups, k), y (B, Cout, T)."""
+import torch
+
+from . import _lib
+from .mpd_ops import _call, _new
+
+
+def out_len(L, k, stride, pad):
+    return (L + 2 * pad - k) // stride + 1
+
+
+def gconv1d_supported(Cin, Cout, groups, k, stride):
+    return bool(_lib.lib().vmasr_gconv1d_supported(int(Cin), int(Cout), int(groups), int(k), int(stride)))
+
+
+def gconv1d_supported_launch(Cin, Cout, groups, k, stride, pad, B, L):
+    """What the three launchers accept (the same predicate they check): the shape, 0 <= pad < k, B and L within one launch."""
+    return bool(_lib.lib().vmasr_gconv1d_supported_launch(int(Cin), int(Cout), int(groups), int(k), int(stride), int(pad), int(B), int(L)))
+
+
+def gconv1d_fwd(x, w, bias, groups, stride, pad, act):
+    """-> (y, pre): y = GELU(pre), pre = conv + bias if act, else y = conv + bias and pre None.  bias may be None."""
+    B, Cin, L = x.shape
+    Cout, _, k = w.shape
+    y = _new(x, (B, Cout, out_len(L, k, stride, pad)))
+    pre = torch.empty_like(y) if act else None
+    _call(_lib.lib().vmasr_gconv1d_fwd, x, w, bias, y, pre, B, Cin, Cout, groups, L, k, stride, pad, int(bool(act)))
+    return y, pre
+
+
+def gconv1d_dgrad(gy, pre, w, x_shape, groups, stride, pad):
+    """-> dx of x_shape from gy (times GELU'(pre) if pre is given)."""
+    B, Cin, L = x_shape
+    Cout, _, k = w.shape
+    dx = _new(gy, x_shape)
+    _call(_lib.lib().vmasr_gconv1d_dgrad, gy, pre, w, dx, B, Cin, Cout, groups, L, k, stride, pad)
+    return dx
+
+
+def gconv1d_wgrad(x, gy, pre, w_shape, groups, stride, pad, want_dw=True, want_db=True):
+    """-> (dw of w_shape, db (Cout,)), each None unless wanted; split-K partials in a workspace, summed in a fixed order."""
+    B, Cin, L = x.shape
+    Cout, _, k = w_shape
+    if not (want_dw or want_db):
+        return None, None
+    nbytes = _lib.lib().vmasr_gconv1d_wgrad_workspace(Cin, Cout, groups, k, stride, pad, B, L)
+    if nbytes == 0:
+        raise RuntimeError(f"gconv1d_wgrad: unsupported shape (Cin={Cin} Cout={Cout} groups={groups} k={k} stride={stride} pad={pad} B={B} L={L})")
+    ws = _new(x, (nbytes // 4,))
+    dw = _new(x, tuple(w_shape)) if want_dw else None
+    db = _new(x, (Cout,)) if want_db else None
+    _call(_lib.lib().vmasr_gconv1d_wgrad, x, gy, pre, dw, db, ws, nbytes, B, Cin, Cout, groups, L, k, stride, pad)
+    return dw, db

@@ -482,6 +482,12 @@ class Trainer(BaseTrainer):
         self.len_epoch = len_epoch if len_epoch is not None else (len(data_loader_train) if data_loader_train is not None else 0)
         self.do_validation = data_loader_val is not None and config.DATA.VALID_SPLIT > 0.0
         self.amp, self.gan = amp, gan
+        # the multi-scale discriminator (vm_asr_amd/msd.py) trains on the eager one-stream step only: no shared fake pass, no second
+        # stream, no graph capture, one process; configs that do not list it take the paths they always took
+        self._msd = bool(gan and "msd" in config.TRAIN.ADVERSARIAL.DISCRIMINATORS and models.get("msd") is not None)
+        if self._msd and self.world > 1:
+            raise NotImplementedError("multi-GPU training with the multi-scale discriminator (DISCRIMINATORS lists 'msd') is not built: "
+                                      "train on one GPU, or with ['mpd'] alone")
         lr_schedulers = lr_schedulers or {}
         self.optimizer_G = optimizers["generator"]
         self.lr_scheduler_G = lr_schedulers.get("generator")
@@ -519,10 +525,17 @@ class Trainer(BaseTrainer):
             # buckets (whole generator = 12 MB in one bucket; MPD 164 MB in ~4)
             self.models["generator"] = DDP(gen, device_ids=ids, bucket_cap_mb=48, gradient_as_bucket_view=True,
                                            broadcast_buffers=False)
-        if self.gan and self.models.get("mpd") is not None and not isinstance(self.models["mpd"], DDP):
-            ids = [self.device.index] if self.device.type == "cuda" else None
-            self.models["mpd"] = DDP(self.models["mpd"], device_ids=ids, bucket_cap_mb=48,
-                                     gradient_as_bucket_view=True, broadcast_buffers=True)
+        for key in self._d_keys():
+            if not isinstance(self.models[key], DDP):
+                ids = [self.device.index] if self.device.type == "cuda" else None
+                self.models[key] = DDP(self.models[key], device_ids=ids, bucket_cap_mb=48,
+                                       gradient_as_bucket_view=True, broadcast_buffers=True)
+
+    def _d_keys(self):
+        """The discriminators this trainer trains, in the reference's order (trainer/trainer.py:337-358): every listed one that was built."""
+        if not self.gan:
+            return []
+        return [k for k in ("mpd", "msd") if k in self.config.TRAIN.ADVERSARIAL.DISCRIMINATORS and self.models.get(k) is not None]
 
     # ---- losses (trainer/trainer.py:88-96, 318-399) ----------------------------------------
     def _init_losses(self):
@@ -536,9 +549,10 @@ class Trainer(BaseTrainer):
         sc, mag = self.multi_resolution_stft(wave_out.squeeze(1), wave_target.squeeze(1))
         return sc + mag
 
-    def _generator_losses(self, wave_out, wave_target, fmap_real=None, fake_pass=None, parts=("signal", "mpd")):
-        """parts: "signal" = the losses on the waveform itself, "mpd" = the ones through the period discriminator (the two-stream
-        step evaluates them on different streams; the dict keeps the reference's order either way)."""
+    def _generator_losses(self, wave_out, wave_target, fmap_real=None, fake_pass=None, parts=("signal", "mpd", "msd")):
+        """parts: "signal" = the losses on the waveform itself, "mpd" / "msd" = the ones through that discriminator (the two-stream
+        step evaluates them on different streams; the dict keeps the reference's order either way).  fmap_real: the period
+        discriminator's real-signal features (the MSD's are recomputed here, as the reference does)."""
         cfg, out = self.config.TRAIN, {}
         wave_out = wave_out.float()
         if "signal" in parts:
@@ -561,6 +575,17 @@ class Trainer(BaseTrainer):
                 out["adversarial_mpd"] = self.higi_gan_loss.generator_loss(y_gen)
             if not cfg.ADVERSARIAL.ONLY_ADVERSARIAL_LOSS:
                 out["features_mpd"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * self.higi_gan_loss.feature_loss(fmap_real, fmap_gen)
+        if "msd" in parts and self._msd:
+            # trainer/trainer.py:401-426.  The weights as constants (the reference's D gradients of this pass are zeroed before
+            # the D loss' backward); the real pass, then the fake pass: the third and fourth power iteration of the step
+            msd = unwrap(self.models["msd"])
+            with torch.no_grad():
+                _, fmap_msd = msd.forward_single(wave_target, detach_weights=True)
+            y_gen, fmap_gen = msd.forward_single(wave_out, detach_weights=True)
+            if not cfg.ADVERSARIAL.ONLY_FEATURE_LOSS:
+                out["adversarial_msd"] = self.higi_gan_loss.generator_loss(y_gen)
+            if not cfg.ADVERSARIAL.ONLY_ADVERSARIAL_LOSS:
+                out["features_msd"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * self.higi_gan_loss.feature_loss(fmap_msd, fmap_gen)
         return out
 
     def _discriminator_losses(self, wave_out, wave_target):
@@ -577,6 +602,10 @@ class Trainer(BaseTrainer):
                 # double backward: runs the discriminator on plain (twice differentiable) torch operators
                 d = d + self.higi_gan_loss.gradient_penalty(wave_target, fake, unwrap(self.models["mpd"]))
             out["mpd"] = d
+        if self._msd:
+            # trainer/trainer.py:401-405: the reference's own call (real, then fake: two power iterations); no gradient penalty
+            y_real, y_gen, _, _ = self.models["msd"](wave_target, wave_out.detach().float())
+            out["msd"] = self.higi_gan_loss.discriminator_loss(y_real, y_gen)
         return out, fmap_real
 
     # ---- flat gradient buffers / single-call all-reduce -------------------------------------
@@ -900,13 +929,16 @@ class Trainer(BaseTrainer):
         Runs BEFORE the generator's backward so that the 164 MB MPD all-reduce can overlap the latter."""
         if not self.gan:
             return
+        keys = self._d_keys() if self._msd else ["mpd"]
         if zero:
-            self._zero_grads("mpd", self.optimizer_D)
+            for key in keys:
+                self._zero_grads(key, self.optimizer_D)
         if st["shared"]:
             st["total_d"].backward(inputs=self._grad_targets("mpd"), retain_graph=True)
         else:
             st["total_d"].backward()
-        self._gather_grads("mpd")
+        for key in keys:
+            self._gather_grads(key)
 
     def _backward_g(self, st, zero=True):
         """Backward of the generator loss — through the (shared) discriminator pass for input gradients only."""
@@ -993,7 +1025,8 @@ class Trainer(BaseTrainer):
             return
         self._backward_d(st, zero)
         if reduce and self.gan:
-            self._reduce_grads("mpd", async_op=True)
+            for key in (self._d_keys() if self._msd else ["mpd"]):
+                self._reduce_grads(key, async_op=True)
         self._backward_g(st, zero)
 
     def _forward_backward(self, wave_input, wave_target, highcut, zero=True):
@@ -1005,7 +1038,7 @@ class Trainer(BaseTrainer):
     def _share_fake_pass(self):
         """One discriminator pass over the generated signal for both losses: GPU, flat gradient buffers (no DDP
         hooks), LSGAN / WGAN without gradient penalty, and the layer-synchronous discriminator path."""
-        if not (self.gan and self.device.type == "cuda" and self.dp_mode == "flat"):
+        if not (self.gan and self.device.type == "cuda" and self.dp_mode == "flat") or self._msd:
             return False
         if self.config.TRAIN.ADVERSARIAL.GAN_LOSS_TYPE == "wgan-gp" or "mpd" not in self.config.TRAIN.ADVERSARIAL.DISCRIMINATORS:
             return False
@@ -1073,12 +1106,14 @@ class Trainer(BaseTrainer):
         if getattr(self, "_hip_adamw_failed", False):
             return None
         from .fused_adamw import HipAdamWStep
-        opts = [("generator", self.optimizer_G)] + ([("mpd", self.optimizer_D)] if self.gan else [])
-        if any(k not in self._flat for k, _ in opts):
+        # every model whose parameters the two optimisers hold needs its flat buffer (the D optimiser holds every listed discriminator)
+        d_keys = self._d_keys() if self._msd else (["mpd"] if self.gan else [])
+        opts = [self.optimizer_G] + ([self.optimizer_D] if self.gan else [])
+        if any(k not in self._flat for k in ["generator"] + d_keys):
             return None
         shadows = {id(src): dst for src, dst in zip(self._shadow_params, self._shadow_dst)}
         try:
-            built = [HipAdamWStep(o, shadows, getattr(self, "_shadow_t", None)) for _, o in opts]
+            built = [HipAdamWStep(o, shadows, getattr(self, "_shadow_t", None)) for o in opts]
         except ValueError as e:
             if "not initialised" in str(e):
                 return None                       # first step: torch creates the state, the next call builds the table
@@ -1088,8 +1123,8 @@ class Trainer(BaseTrainer):
         return built
 
     def _reduce_and_step(self):
-        if self.gan:
-            self._reduce_grads("mpd", async_op=True)
+        for key in (self._d_keys() if self._msd else (["mpd"] if self.gan else [])):
+            self._reduce_grads(key, async_op=True)
         self._reduce_grads("generator", async_op=True)
         self._wait_reduces()
         self._optimizer_steps()
@@ -1109,6 +1144,8 @@ class Trainer(BaseTrainer):
                 continue
             if key != "generator" and self.amp_scope != "step":
                 continue          # the discriminator runs outside autocast in the reference's AMP scope: no bf16 reader
+            if key == "msd":
+                continue          # fp32 with autocast disabled under either scope (vm_asr_amd/msd.py): no bf16 reader
             for p in unwrap(m).parameters():
                 if p.requires_grad and p.dtype == torch.float32:
                     lp = p.detach().to(torch.bfloat16)
@@ -1200,6 +1237,9 @@ class Trainer(BaseTrainer):
         # segmentation fault, with and without round 6's changes); with the collector off across captures AND timed replays: 0 of 38
         # (profiles/r06_replay_segfault.md; a device synchronisation after the collection alone did not help: 2 of 12).  One
         # collection at the end, behind a device synchronisation.  VMASR_GRAPH_GC_GUARD=0: off.
+        if self._msd:      # before anything is captured or allocated
+            raise NotImplementedError("enable_graphs: the step with the multi-scale discriminator (MSD) is eager only; "
+                                      "graph capture covers the generator and ['mpd'] configurations")
         import gc as _gc
         guard = _gc.isenabled() and knobs.get("VMASR_GRAPH_GC_GUARD")
         if guard:
