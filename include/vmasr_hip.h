@@ -700,6 +700,32 @@ int vmasr_gconv1d_dgrad(const float *gy, const float *pre, const float *w, float
 int vmasr_gconv1d_wgrad(const float *x, const float *gy, const float *pre, float *dw, float *db, void *ws, size_t ws_bytes, int32_t B,
                         int32_t Cin, int32_t Cout, int32_t groups, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
 
+/* ---- the scale discriminator's stem: Conv1d(1, Cout, k, stride 1, pad) + bias + GELU without a stored pre-activation
+ *      (vm_asr_amd/csrc/stem1d.hip; model/discriminator.py:181-188) ----
+ *   y[b, o, t] = GELU(bias[o] + sum_{j < k} w[o, j] x[b, t + j - pad]),   x = 0 outside [0, L)
+ * x (B, 1, L), w (Cout, 1, k), bias (Cout) or NULL, y / gy (B, Cout, T) with T = L + 2 pad - k + 1: fp32, contiguous, channel-first.
+ * Plain fp32 FMAs in a fixed order, no float atomics: every result is bit-identical from call to call.
+ * vmasr_stem1d_supported: stride 1, 1 <= k <= 32, 0 <= pad < k, 1 <= Cout <= 65536 (a launch's channel-group grid dimension);
+ * _supported_launch adds 1 <= B <= 65535 and max(1, k - 2 pad) <= L <= 2^28.  The launchers check exactly that predicate; anything
+ * else, a null required pointer included, is VMASR_EINVAL with nothing launched.
+ * fwd: act != 0: y = GELU(conv + bias) (exact erf); act == 0: y = conv + bias.  No pre-activation is written.
+ * bwd: any subset of dx (B, 1, L), dw (Cout, 1, k), db (Cout) (NULL = not wanted, at least one) from gy, x, w, bias and the forward's
+ *      `act`: g = gy GELU'(pre) with pre rebuilt in registers (act == 0: g = gy).  gy is read once for dx and once for dw / db.
+ *      dw / db need ws = vmasr_stem1d_bwd_workspace() bytes (0 for a refused shape): per-slab partials that a second launch adds in a
+ *      fixed order.  Every element of a wanted output is written.
+ * vmasr_stem1d_time_tile / _channel_group: the kernels' time tile and the forward's channels per workgroup (what the tests size
+ * their edge cases by). */
+int32_t vmasr_stem1d_time_tile(void);
+int32_t vmasr_stem1d_channel_group(void);
+int vmasr_stem1d_supported(int32_t Cout, int32_t k, int32_t stride, int32_t pad);
+int vmasr_stem1d_supported_launch(int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+size_t vmasr_stem1d_bwd_workspace(int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+int vmasr_stem1d_fwd(const float *x, const float *w, const float *bias, float *y, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride,
+                     int32_t pad, int32_t act, vmasr_stream_t stream);
+int vmasr_stem1d_bwd(const float *gy, const float *x, const float *w, const float *bias, float *dx, float *dw, float *db, void *ws,
+                     size_t ws_bytes, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad, int32_t act,
+                     vmasr_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) ---------------------
  * When enabled, every kernel launch of this library is bracketed by two hipEvents
  * recorded on the stream the kernel is launched on; vmasr_prof_collect() waits for the
@@ -776,6 +802,9 @@ enum {
     VMASR_K_GCONV1D_DGRAD,      /* its input gradient by residue classes of the stride, GELU' of the incoming gradient on the fly */
     VMASR_K_GCONV1D_WGRAD,      /* its weight / bias gradient: split-K partials into a workspace */
     VMASR_K_GCONV1D_WGRAD_REDUCE, /* the ordered sum of those partials (no float atomics) */
+    VMASR_K_STEM1D_FWD,         /* scale discriminator stem: 1 -> Cout stride-1 convolution + bias + GELU, y only (csrc/stem1d.hip) */
+    VMASR_K_STEM1D_BWD,         /* its backward with the pre-activation rebuilt in registers: dx, or per-slab dw / db partials */
+    VMASR_K_STEM1D_BWD_REDUCE,  /* the ordered sum of those partials (no float atomics) */
     VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };

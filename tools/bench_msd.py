@@ -1,10 +1,12 @@
-"""Times the multi-scale discriminator's grouped convolutions, `hip` (csrc/gconv1d.hip) against `torch` (F.conv1d), and the eager
-["mpd", "msd"] train step.  One process, one device.  Every figure compares the two routes in the same call, ALTERNATING them: after
+"""Times the multi-scale discriminator's grouped convolutions, `hip` (csrc/gconv1d.hip) against `torch` (F.conv1d), its stem (`--stem`:
+csrc/stem1d.hip against F.gelu(F.conv1d), gelu_backward and aten.convolution_backward) and the eager ["mpd", "msd"] train step.  One process, one device.  Every figure compares the two routes in the same call, ALTERNATING them: after
 warm-up calls of both, `--rounds` rounds of (hip window, torch window); a window is n back-to-back calls between two HIP events, n
 chosen per route so that a window lasts about `--window-ms`; the figure of a window is its time / n.  Reported per route: the median,
-the minimum and the maximum of the windows (the spread: a difference inside it is not one).  profiles/msd.md holds the output.
+the minimum and the maximum of the windows (the spread: a difference inside it is not one).  profiles/msd.md and profiles/msd_stem.md
+hold the output.
 
     python tools/bench_msd.py [--batch 4] [--samples 122640] [--rounds 7] [--window-ms 100] [--step] [--out FILE]
+    python tools/bench_msd.py --stem [--step] [...]     # the stem at the three scale lengths, B 4 and 8; --step alternates VMASR_MSD_STEM
 """
 import argparse
 import json
@@ -78,8 +80,47 @@ def layer_rows(batch, samples, rounds, window_ms, hidden=128):
     return rows
 
 
-def step_ms(batch, samples, rounds, steps=4):
-    """One trainer; VMASR_MSD_CONV is read at every call, so the two routes alternate in windows of `steps` steps on the same state."""
+STEM_K, STEM_PAD, STEM_LENGTHS, STEM_BATCHES = 15, 7, (122640, 61321, 30661), (4, 8)
+
+
+def stem_rows(rounds, window_ms, hidden=128):
+    """The stem (1 -> hidden, k 15, stride 1, pad 7) at the three scale lengths: forward, backward for dw + db (the discriminator's
+    pass), backward for dx alone (the generator's pass).  GB/s: the fused route's own minimal traffic (the map once + x + the taps)."""
+    from vm_asr_amd import msd_ops
+    g_in, rows = torch.ops.aten.gelu_backward, []
+    for batch in STEM_BATCHES:
+        for L in STEM_LENGTHS:
+            x = torch.randn(batch, 1, L, device="cuda")
+            w = torch.randn(hidden, 1, STEM_K, device="cuda") / STEM_K ** 0.5
+            b = torch.randn(hidden, device="cuda")
+            gy = torch.randn(batch, hidden, L, device="cuda")
+            pre = F.conv1d(x, w, b, 1, STEM_PAD)
+
+            def cb(mask):
+                return torch.ops.aten.convolution_backward(g_in(gy, pre), x, w, [hidden], [1], [STEM_PAD], [1], False, [0], 1, mask)
+            small = 4.0 * (batch * L + hidden * (STEM_K + 1))
+            nbytes = {"fwd": 4.0 * gy.numel() + small, "bwd_w": 4.0 * gy.numel() + small, "bwd_x": 4.0 * gy.numel() + small + 4.0 * batch * L}
+            ops = {
+                "fwd": {"hip": lambda: msd_ops.stem1d_fwd(x, w, b, STEM_PAD, True), "torch": lambda: F.gelu(F.conv1d(x, w, b, 1, STEM_PAD))},
+                "bwd_w": {"hip": lambda: msd_ops.stem1d_bwd(gy, x, w, b, STEM_PAD, True, False, True, True),
+                          "torch": lambda: cb([False, True, True])},
+                "bwd_x": {"hip": lambda: msd_ops.stem1d_bwd(gy, x, w, b, STEM_PAD, True, True, False, False),
+                          "torch": lambda: cb([True, False, False])},
+            }
+            row = {"layer": "convs.0", "B": batch, "Cout": hidden, "L": L, "map_MB": round(4.0 * gy.numel() / 1e6, 1)}
+            for op, fns in ops.items():
+                for route, r in compare(fns, rounds, window_ms).items():
+                    row[f"{route}_{op}_ms"], row[f"{route}_{op}_min"], row[f"{route}_{op}_max"] = r["ms"], r["min"], r["max"]
+                    row[f"{route}_{op}_calls"] = r["calls"]
+                row[f"hip_{op}_GBps"] = round(nbytes[op] / row[f"hip_{op}_ms"] / 1e6, 1)
+            rows.append(row)
+            del x, w, b, gy, pre
+    return rows
+
+
+def step_ms(batch, samples, rounds, steps=4, knob="VMASR_MSD_CONV"):
+    """One trainer; `knob` (VMASR_MSD_CONV, or VMASR_MSD_STEM for the stem alone) is read at every call, so the two routes alternate
+    in windows of `steps` steps on the same state."""
     from vm_asr_amd import get_model
     from vm_asr_amd.config import get_default_config, update_config
     from vm_asr_amd.trainer import SyntheticVCTK, Trainer, build_optimizer
@@ -105,15 +146,15 @@ def step_ms(batch, samples, rounds, steps=4):
     wave_in, wave, hf = inp.to(dev), tgt.to(dev), hc.to(dev)
     ms = {"hip": [], "torch": []}
     for mode in ms:                    # warm-up of both routes
-        os.environ["VMASR_MSD_CONV"] = mode
+        os.environ[knob] = mode
         for _ in range(3):
             tr.train_step(wave_in, wave, hf)
     torch.cuda.synchronize()
     for _ in range(rounds):
         for mode in ms:
-            os.environ["VMASR_MSD_CONV"] = mode
+            os.environ[knob] = mode
             ms[mode].append(_window(lambda: tr.train_step(wave_in, wave, hf), steps))
-    os.environ.pop("VMASR_MSD_CONV")
+    os.environ.pop(knob)
     return {k: {"ms": statistics.median(v), "min": min(v), "max": max(v), "calls": steps} for k, v in ms.items()}
 
 
@@ -124,14 +165,15 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--window-ms", type=float, default=100.0)
     ap.add_argument("--step", action="store_true", help="also time the eager ['mpd', 'msd'] train step, hip and torch alternated")
+    ap.add_argument("--stem", action="store_true", help="time the stem (csrc/stem1d.hip) instead of the grouped layers; --step then alternates VMASR_MSD_STEM")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "batch": a.batch, "samples": a.samples, "rounds": a.rounds, "window_ms": a.window_ms,
-           "layers": layer_rows(a.batch, a.samples, a.rounds, a.window_ms)}
+           "layers": stem_rows(a.rounds, a.window_ms) if a.stem else layer_rows(a.batch, a.samples, a.rounds, a.window_ms)}
     for r in res["layers"]:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
     if a.step:
-        res["step"] = step_ms(a.batch, a.samples, a.rounds)
+        res["step"] = step_ms(a.batch, a.samples, a.rounds, knob="VMASR_MSD_STEM" if a.stem else "VMASR_MSD_CONV")
         print(json.dumps({"step": {k: {n: round(x, 2) for n, x in v.items()} for k, v in res["step"].items()}}), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -209,6 +209,13 @@ SYMBOLS = {
     "vmasr_gconv1d_fwd": (ctypes.c_int, [c_vp] * 5 + [c_i32] * 4 + [c_i64] + [c_i32] * 4 + [c_vp]),
     "vmasr_gconv1d_dgrad": (ctypes.c_int, [c_vp] * 4 + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
     "vmasr_gconv1d_wgrad": (ctypes.c_int, [c_vp] * 6 + [c_sz] + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
+    "vmasr_stem1d_time_tile": (c_i32, []),
+    "vmasr_stem1d_channel_group": (c_i32, []),
+    "vmasr_stem1d_supported": (ctypes.c_int, [c_i32] * 4),
+    "vmasr_stem1d_supported_launch": (ctypes.c_int, [c_i32] * 5 + [c_i64]),
+    "vmasr_stem1d_bwd_workspace": (c_sz, [c_i32] * 5 + [c_i64]),
+    "vmasr_stem1d_fwd": (ctypes.c_int, [c_vp] * 4 + [c_i32] * 2 + [c_i64] + [c_i32] * 4 + [c_vp]),
+    "vmasr_stem1d_bwd": (ctypes.c_int, [c_vp] * 8 + [c_sz] + [c_i32] * 2 + [c_i64] + [c_i32] * 4 + [c_vp]),
     "vmasr_resample_poly": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_resample_design_workspace": (c_sz, [c_i32]),
     "vmasr_resample_design": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
@@ -334,7 +341,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 70
+K_COUNT = 73
 
 
 def zeros_f32(device, *shapes):

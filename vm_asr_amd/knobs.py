@@ -4,7 +4,7 @@
 outside the declared set raises ValueError at the read.  Nothing else under vm_asr_amd/ reads a VMASR_* variable.  Readers:
 "python" = this package through get(), for the switches that existed when this registry was written: tests/test_knobs.py pins exactly
 that set and its defaults in a fixed table.  A python-read switch added later cannot join the table, so it carries "python:<feature>"
-(so far "python:msd") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py);
+(so far "python:msd") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py);
 "csrc" = a static `getenv` in vm_asr_amd/csrc (read once per process; listed here with the
 default the C++ code applies); "external" = bench.py, the tests, tools/ or oracle/, which read their own names directly.
 No torch import: tests/test_knobs.py and tools load this module without a GPU stack.
@@ -134,6 +134,8 @@ KNOBS = {k.name: k for k in (
     # ---- scale discriminator
     _k("VMASR_MSD_CONV", "choice", "hip", "the MSD's strided grouped 1-D convolutions: hip = the exact-fp32 MFMA kernels (csrc/gconv1d.hip), "
        "torch = F.conv1d (A/B measurements, double backward)", values=("hip", "torch"), reader="python:msd"),
+    _k("VMASR_MSD_STEM", "choice", "hip", "the MSD's 1 -> hidden stem convolution + GELU: hip = one fused pass that keeps no pre-activation "
+       "(csrc/stem1d.hip), torch = F.conv1d + F.gelu (A/B measurements, double backward)", values=("hip", "torch"), reader="python:msd"),
     # ---- train step
     _k("VMASR_TWO_STREAM", "choice", "1", "the discriminator on a side stream: 1 on, 0 one stream, force also in deterministic mode (test hook)",
        values=("1", "0", "force")),

@@ -11,9 +11,12 @@ How it runs:
   * CPU tensors: plain torch (F.conv1d + F.gelu), like the MPD.
   * GPU: the five strided grouped convolutions (k 41, stride 4, pad 20, groups 4 / 16) run on csrc/gconv1d.hip — exact-fp32 MFMA
     forward with bias + GELU in the epilogue, input gradient by stride residue classes, weight gradient as split-K partials with an
-    ordered sum (bit-identical from run to run).  The three dense layers (1 -> h k 15, 8h -> 8h k 5, 8h -> 1 k 3) and the pools are
-    torch operators.  VMASR_MSD_CONV=torch routes the grouped layers through F.conv1d too (A/B measurements; and what
-    discriminator.plain_torch_ops selects: the HIP functions are differentiable once).
+    ordered sum (bit-identical from run to run).  The stem (1 -> h, k 15, stride 1: the one layer at the waveform rate, the largest
+    map of the module) runs on csrc/stem1d.hip: convolution + bias + GELU in one pass that writes y only; its backward rebuilds the
+    pre-activation in registers from x, w and bias, so nothing of the map's size is kept for it, and its dw / db are ordered sums too.
+    The two remaining dense layers (8h -> 8h k 5, 8h -> 1 k 3) and the pools are torch operators.  VMASR_MSD_CONV=torch routes every
+    layer through F.conv1d (A/B measurements; and what discriminator.plain_torch_ops selects: the HIP functions are differentiable
+    once); VMASR_MSD_STEM=torch does that for the stem alone.
   * The module computes in fp32 with autocast disabled, so amp_scope="step" leaves the MSD in fp32.
   * Spectral norm follows the reference's schedule exactly: one power iteration per training forward of a ScaleDiscriminator, the
     weight normalised anew in every pass (the layers read their parametrization directly, so an enclosing
@@ -28,7 +31,7 @@ from torch.nn.utils.parametrizations import weight_norm
 from . import knobs, msd_ops as bind
 from .discriminator import _PLAIN_OPS, _SpectralNorm, spectral_norm
 
-__all__ = ["ScaleDiscriminator", "MultiScaleDiscriminator", "grouped_conv1d"]
+__all__ = ["ScaleDiscriminator", "MultiScaleDiscriminator", "grouped_conv1d", "stem_conv1d"]
 
 
 class _GConv1dFn(torch.autograd.Function):
@@ -52,6 +55,46 @@ class _GConv1dFn(torch.autograd.Function):
         dx = bind.gconv1d_dgrad(gy, pre, w, x.shape, groups, stride, pad) if need_x else None
         dw, db = bind.gconv1d_wgrad(x, gy, pre, w.shape, groups, stride, pad, need_w, need_b)
         return dx, dw, db, None, None, None, None
+
+
+class _Stem1dFn(torch.autograd.Function):
+    """y = [GELU](conv1d(x, w, bias, 1, pad)) for one input channel on csrc/stem1d.hip; saves x, w and bias: nothing of y's size."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, pad, act):
+        x, w = x.contiguous(), w.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        ctx.save_for_backward(x, w, bias)
+        ctx.geom = (pad, act)
+        return bind.stem1d_fwd(x, w, bias, pad, act)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w, bias = ctx.saved_tensors
+        pad, act = ctx.geom
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], bias is not None and ctx.needs_input_grad[2]
+        dx, dw, db = bind.stem1d_bwd(gy.contiguous(), x, w, bias, pad, act, need_x, need_w, need_b)
+        return dx, dw, db, None, None
+
+
+def _stem_ok(x, w, bias, stride, pad):
+    if not x.is_cuda or _PLAIN_OPS[0] or knobs.get("VMASR_MSD_CONV") != "hip" or knobs.get("VMASR_MSD_STEM") != "hip":
+        return False
+    if any(t.dtype != torch.float32 or not t.is_cuda for t in (x, w) + (() if bias is None else (bias,))):
+        return False
+    if x.dim() != 3 or w.dim() != 3 or x.shape[1] != 1 or w.shape[1] != 1:
+        return False
+    return bind.stem1d_supported_launch(w.shape[0], w.shape[2], stride, pad, x.shape[0], x.shape[2])
+
+
+def stem_conv1d(x, w, bias, stride, pad, act):
+    """[GELU](F.conv1d(x, w, bias, stride, pad)) of a one-channel x: the fused HIP pass where vmasr_stem1d_supported_launch accepts the
+    call (fp32 on the GPU, VMASR_MSD_CONV=hip, VMASR_MSD_STEM=hip, plain_torch_ops off), torch's operators otherwise."""
+    if _stem_ok(x, w, bias, stride, pad):
+        return _Stem1dFn.apply(x, w, bias, pad, act)
+    y = F.conv1d(x, w, bias, stride, pad)
+    return F.gelu(y) if act else y
 
 
 def _hip_ok(x, w, groups, stride, pad):
@@ -110,6 +153,8 @@ class ScaleDiscriminator(nn.Module):
                 act = layer is not self.conv_post
                 if layer.groups > 1:
                     x = grouped_conv1d(x, w, b, layer.groups, layer.stride[0], layer.padding[0], act)
+                elif layer.in_channels == 1 and layer.stride[0] == 1:
+                    x = stem_conv1d(x, w, b, 1, layer.padding[0], act)
                 else:
                     x = F.conv1d(x, w, b, layer.stride, layer.padding)
                     if act:

@@ -1,8 +1,8 @@
-"""The scale discriminator's HIP entry points (include/vmasr_hip.h, csrc/gconv1d.hip), one Python function each — the companion of
-mpd_ops.py.
+"""The scale discriminator's HIP entry points (include/vmasr_hip.h, csrc/gconv1d.hip, csrc/stem1d.hip), one Python function each — the
+companion of mpd_ops.py.
 
 Every function takes tensors and plain numbers, allocates its outputs and launches through _lib.call.  No autograd and no switches here:
-vm_asr_amd/msd.py decides what runs.  Layout: channel-first fp32, x (B, Cin, L), w (Cout, Cin / groups, k), y (B, Cout, T)."""
+vm_asr_amd/msd.py decides what runs.  Layout: channel-first fp32, x (B, Cin, L), w (Cout, Cin / groups, k), y (B, Cout, T); the stem has Cin = groups = stride = 1."""
 import torch
 
 from . import _lib
@@ -55,3 +55,47 @@ def gconv1d_wgrad(x, gy, pre, w_shape, groups, stride, pad, want_dw=True, want_d
     db = _new(x, (Cout,)) if want_db else None
     _call(_lib.lib().vmasr_gconv1d_wgrad, x, gy, pre, dw, db, ws, nbytes, B, Cin, Cout, groups, L, k, stride, pad)
     return dw, db
+
+
+def stem1d_time_tile():
+    """Positions of one workgroup pass of the stem kernels (the tests size their edge cases by it)."""
+    return int(_lib.lib().vmasr_stem1d_time_tile())
+
+
+def stem1d_channel_group():
+    """Output channels of one workgroup of the stem's forward."""
+    return int(_lib.lib().vmasr_stem1d_channel_group())
+
+
+def stem1d_supported_launch(Cout, k, stride, pad, B, L):
+    """What vmasr_stem1d_fwd / _bwd accept (the same predicate they check)."""
+    return bool(_lib.lib().vmasr_stem1d_supported_launch(int(Cout), int(k), int(stride), int(pad), int(B), int(L)))
+
+
+def stem1d_fwd(x, w, bias, pad, act):
+    """-> y = GELU(conv1d(x, w, bias, 1, pad)) if act, else the convolution + bias; x (B, 1, L), w (Cout, 1, k).  No pre-activation."""
+    B, _, L = x.shape
+    Cout, _, k = w.shape
+    y = _new(x, (B, Cout, out_len(L, k, 1, pad)))
+    _call(_lib.lib().vmasr_stem1d_fwd, x, w, bias, y, B, Cout, L, k, 1, pad, int(bool(act)))
+    return y
+
+
+def stem1d_bwd(gy, x, w, bias, pad, act, want_dx=True, want_dw=True, want_db=True):
+    """-> (dx (B, 1, L), dw (Cout, 1, k), db (Cout,)), each None unless wanted, from gy and the forward's operands (the pre-activation
+    is rebuilt in registers).  dw / db: per-slab partials in a workspace, summed in a fixed order."""
+    B, _, L = x.shape
+    Cout, _, k = w.shape
+    if not (want_dx or want_dw or want_db):
+        return None, None, None
+    ws, nbytes = None, 0
+    if want_dw or want_db:
+        nbytes = _lib.lib().vmasr_stem1d_bwd_workspace(Cout, k, 1, pad, B, L)
+        if nbytes == 0:
+            raise RuntimeError(f"stem1d_bwd: unsupported shape (Cout={Cout} k={k} pad={pad} B={B} L={L})")
+        ws = _new(x, (nbytes // 4,))
+    dx = _new(x, tuple(x.shape)) if want_dx else None
+    dw = _new(x, tuple(w.shape)) if want_dw else None
+    db = _new(x, (Cout,)) if want_db else None
+    _call(_lib.lib().vmasr_stem1d_bwd, gy, x, w, bias, dx, dw, db, ws, nbytes, B, Cout, L, k, 1, pad, int(bool(act)))
+    return dx, dw, db
