@@ -192,15 +192,15 @@ def test_stream_layouts_agree_with_the_one_stream_step(monkeypatch):
             unwrap(m).load_state_dict(state[k])
         tr2._refresh_shadows()
         snap2 = tr2._snapshot_training_state()
-        names = {key: [f"{key}.{n}" for n, p in unwrap(tr2.models[key]).named_parameters() if any(p is q for q in tr2._flat_params[key])]
-                 for key in tr2._flat_params}
+        names = {key: [f"{key}.{n}" for n, p in unwrap(tr2.models[key]).named_parameters() if any(p is q for q in tr2.grads.params[key])]
+                 for key in tr2.grads.params}
         for it in range(10):
             tr2._restore_training_state(snap2)
             torch.manual_seed(77)
             torch.cuda.manual_seed_all(77)
             tr2._graphed(*batch)
             torch.cuda.synchronize()
-            got = {nme: v.detach().clone() for key in tr2._flat_params for nme, v in zip(names[key], tr2._flat_views[key])}
+            got = {nme: v.detach().clone() for key in tr2.grads.params for nme, v in zip(names[key], tr2.grads.views[key])}
             assert got.keys() == ref.keys()
             worst[f"captured, {pin}"] = max(worst.get(f"captured, {pin}", (0.0, None)), _dist(got, ref))
         del tr2
@@ -231,7 +231,7 @@ def test_captured_generator_only_step_in_deterministic_mode():
             torch.cuda.manual_seed_all(77)
             tr._graphed(*batch)
             torch.cuda.synchronize()
-            runs.append(tr._flat["generator"].detach().clone())
+            runs.append(tr.grads.flat["generator"].detach().clone())
         assert torch.isfinite(runs[0]).all() and runs[0].abs().max() > 0
         assert all(torch.equal(runs[0], r) for r in runs[1:])
         assert lib.vmasr_det_timeouts() == 0

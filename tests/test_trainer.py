@@ -920,12 +920,12 @@ def _flat8_worker(rank, world, port, ret):
     full = _batch(cfg, world, seed=11)
     with oracle_stft_patch():
         _, logs = tr._forward_backward(*(t[rank:rank + 1] for t in full))
-        local = {k: tr._flat[k].clone() if k in tr._flat else None for k in ("generator", "mpd")}
+        local = {k: tr.grads.flat[k].clone() if k in tr.grads.flat else None for k in ("generator", "mpd")}
         if local["generator"] is None:      # flat buffers are set up lazily by the first reduce
-            tr._setup_flat("generator", tr.optimizer_G); tr._setup_flat("mpd", tr.optimizer_D)
-            local = {k: tr._flat[k].clone() for k in ("generator", "mpd")}
+            tr.grads.setup("generator"); tr.grads.setup("mpd")
+            local = {k: tr.grads.flat[k].clone() for k in ("generator", "mpd")}
         tr._reduce_and_step()
-    ret[rank] = dict(local={k: v for k, v in local.items()}, reduced={k: tr._flat[k].clone() for k in local},
+    ret[rank] = dict(local={k: v for k, v in local.items()}, reduced={k: tr.grads.flat[k].clone() for k in local},
                      sd={k: v.detach().clone() for k, v in unwrap(tr.models["generator"]).state_dict().items()})
     dist.barrier()
     dist.destroy_process_group()

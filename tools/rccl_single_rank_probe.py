@@ -30,14 +30,14 @@ def run(tag, in_graph):
     replays on new batches (losses printed: must agree between the layouts), then 20 timed steps."""
     os.environ["VMASR_GRAPH_COLLECTIVES"] = "1" if in_graph else "0"
     tr = bench.build_trainer(cfg, dev, amp=True, capturable=True)
-    tr.world = 2
+    tr.world = tr.grads.world = 2
     for m in tr.models.values():
         m.train()
     _, logs = tr.train_step(*batches[0])
     print(f"[{tag}] eager + RCCL all-reduce (issued behind the D backward on the side stream):", {k: round(float(v), 4) for k, v in logs.items()})
     ok = tr.enable_graphs(batches[0], warmup=2)
     print(f"[{tag}] graph capture with the RCCL process group alive: {ok}; collectives captured into the graph: "
-          f"{tr._graphed.collectives_in_graph}; MPD wire dtype {tr._comm_dtype('mpd')}, generator {tr._comm_dtype('generator')}")
+          f"{tr._graphed.collectives_in_graph}; MPD wire dtype {tr.grads.comm_dtype('mpd')}, generator {tr.grads.comm_dtype('generator')}")
     assert ok and tr._graphed.collectives_in_graph == in_graph
     seen = []
     for b in batches[1:]:

@@ -44,7 +44,7 @@ def run(tag, env):
     os.environ.update(env)
     tr = bench.build_trainer(cfg, dev, amp=True, capturable=True)        # seeded construction: identical initial weights on every rank
     if FAKE:
-        tr.world = 2
+        tr.world = tr.grads.world = 2
     for m in tr.models.values():
         m.train()
     tr.train_step(*batches[0])
@@ -64,7 +64,7 @@ def run(tag, env):
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
     spread = float((hi - lo).abs().max())
-    info = dict(in_graph=bool(tr._graphed.collectives_in_graph), mpd_wire=str(tr._comm_dtype("mpd")), spread=spread)
+    info = dict(in_graph=bool(tr._graphed.collectives_in_graph), mpd_wire=str(tr.grads.comm_dtype("mpd")), spread=spread)
     if rank == 0:
         print(f"[{tag}] {info} losses {[ [round(float(v), 4) for v in l] for l in losses]}", flush=True)
     del tr

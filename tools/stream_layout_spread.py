@@ -125,7 +125,7 @@ def main():
                 mb.load_state_dict(ma.state_dict())
         tr2._refresh_shadows()
         snap2 = tr2._snapshot_training_state()
-        names = {key: [f"{key}.{n}" for n, p in m.named_parameters() if any(p is q for q in tr2._flat_params[key])] for key, m in tr2.models.items()}
+        names = {key: [f"{key}.{n}" for n, p in m.named_parameters() if any(p is q for q in tr2.grads.params[key])] for key, m in tr2.models.items()}
 
         def replay():
             tr2._restore_training_state(snap2)
@@ -134,8 +134,8 @@ def main():
             tr2._graphed(*batch)
             torch.cuda.synchronize()
             out = {}
-            for key in tr2._flat_params:
-                for nme, v in zip(names[key], tr2._flat_views[key]):
+            for key in tr2.grads.params:
+                for nme, v in zip(names[key], tr2.grads.views[key]):
                     out[nme] = v.detach().clone()
             return out
         from vm_asr_amd.trainer import unwrap

@@ -1,6 +1,7 @@
 """Training and evaluation on a folder of wav files: the reference's data loader (data_loader/data_loaders.py:25-79,82-520) with
 every signal-processing step on the device.
 
+    SyntheticVCTK(config, length, sr_in, seed)               dataset of seeded noise clips with the same batch contract (no files)
     WavFolder(config, training, root=None)                   dataset: (wave (1, n) CPU, file_sr, name) per clip, nothing else
     collate_clips(samples)                                   -> (waves (B, 1, n_max) zero-padded, lengths, rates, names)
     PrepareOnDevice(loader, config, device, training, seed)  yields (wave_in, wave_tgt, highcut, name, pad) on `device`
@@ -29,7 +30,30 @@ from . import resample
 from .inferencer import read_wav
 from .tester import frames_per_segment
 
-__all__ = ["WavFolder", "collate_clips", "PrepareOnDevice", "get_loader"]
+__all__ = ["SyntheticVCTK", "WavFolder", "collate_clips", "PrepareOnDevice", "get_loader"]
+
+
+class SyntheticVCTK(torch.utils.data.Dataset):
+    """Synthetic clips with the reference's batch contract
+    `(wave_in (1,T), wave_tgt (1,T), highcut int64, name, pad)` — CustomVCTK_092._load_sample
+    (data_loader/data_loaders.py:490-513); T = int(SEGMENT * TARGET_SR) (:138-140);
+    highcut = int((n_fft/2+1) * sr_in / sr_tgt) (:482-486).  Seeds follow SURVEY.md §8d."""
+
+    def __init__(self, config, length=64, sr_in=16000, seed=123):
+        self.T = int(config.DATA.SEGMENT * config.DATA.TARGET_SR)
+        self.n = length
+        self.seed = seed
+        self.highcut = int((config.DATA.STFT.N_FFT // 2 + 1) * sr_in / config.DATA.TARGET_SR)
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(self.seed + i)
+        tgt = 0.1 * torch.randn(1, self.T, generator=g)
+        g2 = torch.Generator().manual_seed(self.seed + 1 + 7919 * (i + 1))
+        inp = 0.1 * torch.randn(1, self.T, generator=g2)
+        return inp, tgt, torch.tensor(self.highcut, dtype=torch.int64), f"synthetic_{i:06d}", 0
 
 
 class WavFolder(torch.utils.data.Dataset):
@@ -83,7 +107,7 @@ def pad_length(n, seg):
 
 
 class PrepareOnDevice:
-    """Wraps a loader of `collate_clips` batches; yields the batch contract of trainer.SyntheticVCTK,
+    """Wraps a loader of `collate_clips` batches; yields the batch contract of SyntheticVCTK,
     `(wave_in (B,1,T), wave_tgt (B,1,T), highcut (B) int64, names, pad (B) int64)`, waves on `device`.  Training: T is the segment
     and the input rate of each clip is drawn (uniformly from DATA.RANDOM_RESAMPLE, or by DATA.WEIGHTED_SR as data_loaders.py:439-453)
     from random.Random(seed) / numpy.random.default_rng(seed); testing: T is the longest clip padded to a multiple of the segment

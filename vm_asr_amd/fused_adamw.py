@@ -32,7 +32,7 @@ class HipAdamWStep:
             raise ValueError("param groups differ in betas / eps")
         lr = g0["lr"]
         if not (torch.is_tensor(lr) and lr.is_cuda and all(g["lr"] is lr for g in groups)):
-            raise ValueError("needs ONE device learning-rate tensor shared by the param groups (trainer.lr_to_device)")
+            raise ValueError("needs ONE device learning-rate tensor shared by the param groups (optim.lr_to_device)")
         self.lr = lr if lr.dtype == torch.float32 else None
         if self.lr is None:
             raise ValueError("learning-rate tensor must be float32")

@@ -26,7 +26,7 @@ One-stream layout (VMASR_TWO_STREAM=0, deterministic mode, no shared fake pass) 
     graph B   as above
 
 The graphs of a layout share one memory pool and one autograd graph (built while the first is captured, consumed while the
-next is — the fwd/bwd split torch.cuda.make_graphed_callables uses).  The learning rate is a device tensor (trainer.lr_to_device),
+next is — the fwd/bwd split torch.cuda.make_graphed_callables uses).  The learning rate is a device tensor (optim.lr_to_device),
 so a scheduler update between replays takes effect in graph B.
 
 The library's own kernels are launched on the capturing stream through ctypes, so they are part of
@@ -98,6 +98,7 @@ class GraphedTrainStep:
         from . import _lib
         _lib.prof_enable(False)
         self.static_in = [t.clone() for t in example_batch]
+        self.d_keys = tr._d_keys()          # the discriminators of the captured step (enable_graphs: the MPD alone)
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
         side.wait_stream(cur)
@@ -105,14 +106,13 @@ class GraphedTrainStep:
             for i in range(max(2, warmup)):
                 tr._forward_backward(*self.static_in)
                 if i == 0:  # flat buffers exist before anything is captured
-                    tr._setup_flat("generator", tr.optimizer_G)
-                    if tr.gan:
-                        tr._setup_flat("mpd", tr.optimizer_D)
+                    for key in ["generator"] + self.d_keys:
+                        tr.grads.setup(key)
                 tr._reduce_and_step()
         cur.wait_stream(side)
         torch.cuda.synchronize()
         for opt in [tr.optimizer_G] + ([tr.optimizer_D] if tr.gan else []):
-            from .trainer import lr_to_device
+            from .optim import lr_to_device
             if any(torch.is_tensor(g["lr"]) and not g["lr"].is_cuda for g in opt.param_groups):
                 lr_to_device(opt, tr.device)      # a host lr would be frozen into graph B at capture
         # world_size > 1 on RCCL with VMASR_GRAPH_COLLECTIVES=1: the gradient all-reduces are captured INTO graph A (branches of the same
@@ -130,15 +130,15 @@ class GraphedTrainStep:
             # round first: RCCL sets up its channels / buffers on the first collective of a communicator, which must not happen
             # inside a capture
             try:
-                comm = tr.enable_direct_rccl()      # (raises on EVERY rank if it failed on any: rccl.RcclComm agrees by all-reduce(MIN))
+                comm = tr.grads.enable_direct_rccl()      # (raises on EVERY rank if it failed on any: rccl.RcclComm agrees by all-reduce(MIN))
             except RuntimeError as e:
                 tr.logger.warning(f"{e}: the gradient all-reduces stay between the graphs")
                 tr._graph_collectives = False
                 self.collectives_in_graph = False
         self.watchdog = None
         if self.collectives_in_graph:
-            for key in (["mpd"] if tr.gan else []) + ["generator"]:
-                comm.all_reduce_(torch.zeros_like(tr._flat[key], dtype=tr._comm_dtype(key)), avg=True, stream=tr._comm_stream())
+            for key in self.d_keys + ["generator"]:
+                comm.all_reduce_(torch.zeros_like(tr.grads.flat[key], dtype=tr.grads.comm_dtype(key)), avg=True, stream=tr.grads._comm_stream())
             torch.cuda.synchronize()
             from .rccl import CollectiveWatchdog
             self.watchdog = CollectiveWatchdog()     # nothing else watches a captured collective: the rank exits non-zero if one hangs
@@ -164,8 +164,8 @@ class GraphedTrainStep:
             if st.get("two"):      # two-stream step: ONE graph with a fork / join (the branches run concurrently on replay)
                 tr._backward_both(st, reduce=self.collectives_in_graph)
                 if self.collectives_in_graph:
-                    tr._reduce_grads("generator", async_op=True)
-                    tr._wait_reduces()                       # the join of the collective branches: last node(s) of graph A
+                    tr.grads.reduce("generator", async_op=True)
+                    tr.grads.wait()                       # the join of the collective branches: last node(s) of graph A
             else:
                 tr._backward_d(st)
         self.graph_g = None
@@ -189,11 +189,11 @@ class GraphedTrainStep:
             done.record()                       # behind graph A (outside any capture: queryable)
             self.watchdog.arm(done, "the gradient all-reduce captured into the step's graph")
         if not self.collectives_in_graph:
-            if self.tr.gan:
-                self.tr._reduce_grads("mpd", async_op=True)   # (between the graphs: exposed — a graph launch does not overlap another stream)
+            for key in self.d_keys:
+                self.tr.grads.reduce(key, async_op=True)      # (between the graphs: exposed — a graph launch does not overlap another stream)
             if self.graph_g is not None:
                 self.graph_g.replay()
-            self.tr._reduce_grads("generator", async_op=True)
-            self.tr._wait_reduces()
+            self.tr.grads.reduce("generator", async_op=True)
+            self.tr.grads.wait()
         self.graph_opt.replay()
         return self.static_out, self.static_logs

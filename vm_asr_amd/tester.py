@@ -20,7 +20,7 @@ import wave
 
 import torch
 
-from .trainer import _Logger, unwrap
+from .optim import unwrap
 
 __all__ = ["unfold_audio", "fold_audio", "frames_per_segment", "write_pcm16", "device_sync", "enhance", "BaseTester", "Tester"]
 
@@ -85,6 +85,7 @@ def enhance(gen, wave_input, highcut, segment_length, overlap, segment_batch=1):
 
 class BaseTester:
     def __init__(self, models, metric_ftns, config, logger=None):
+        from .trainer import _Logger      # (not at the top: trainer imports data, which imports this module)
         self.config, self.logger = config, logger or _Logger()
         self.models, self.metric_ftns = models, metric_ftns
         tag = str(config.TAG).split("_")

@@ -7,7 +7,7 @@ not have (README.md:31):
 
   * one process per GPU, `torch.distributed` backend "nccl" (= RCCL over xGMI); the clip batch
     is sharded across ranks; every model's gradients are packed into ONE flat fp32 buffer and
-    all-reduced by one call per model per step (dp_mode "flat": few large messages suit the
+    all-reduced by one call per model per step (dp_mode "flat", grad_sync.FlatGrads: few large messages suit the
     point-to-point xGMI links, and the step stays HIP-graph capturable); torch DDP buckets
     overlapped with backward are the alternative dp_mode "ddp".  No data-path collective (SURVEY.md §8e);
   * the 129 `layers_decoder_phase` tensors never receive a gradient in the reference either
@@ -36,7 +36,11 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 
 from . import knobs
 from . import metric as metric_mod
+from .data import SyntheticVCTK
+from .grad_sync import FlatGrads
 from .loss import HiFiGANLoss, MultiResolutionSTFTLoss, mae_loss, mse_loss
+from .optim import (_RUNTIME_GROUP_KEYS, CosineWarmupScheduler, build_optimizer, load_optimizer_state, lr_to_device,  # noqa: F401
+                    portable_optimizer_state, set_weight_decay, unwrap)
 
 __all__ = ["BaseTrainer", "Trainer", "SyntheticVCTK", "CosineWarmupScheduler", "build_optimizer",
            "set_weight_decay", "init_distributed", "unwrap"]
@@ -89,151 +93,6 @@ def distributed_info(device):
     return info
 
 
-def unwrap(m):
-    return m.module if isinstance(m, DDP) else m
-
-
-class SyntheticVCTK(torch.utils.data.Dataset):
-    """Synthetic clips with the reference's batch contract
-    `(wave_in (1,T), wave_tgt (1,T), highcut int64, name, pad)` — CustomVCTK_092._load_sample
-    (data_loader/data_loaders.py:490-513); T = int(SEGMENT * TARGET_SR) (:138-140);
-    highcut = int((n_fft/2+1) * sr_in / sr_tgt) (:482-486).  Seeds follow SURVEY.md §8d."""
-
-    def __init__(self, config, length=64, sr_in=16000, seed=123):
-        self.T = int(config.DATA.SEGMENT * config.DATA.TARGET_SR)
-        self.n = length
-        self.seed = seed
-        self.highcut = int((config.DATA.STFT.N_FFT // 2 + 1) * sr_in / config.DATA.TARGET_SR)
-
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        g = torch.Generator().manual_seed(self.seed + i)
-        tgt = 0.1 * torch.randn(1, self.T, generator=g)
-        g2 = torch.Generator().manual_seed(self.seed + 1 + 7919 * (i + 1))
-        inp = 0.1 * torch.randn(1, self.T, generator=g2)
-        return inp, tgt, torch.tensor(self.highcut, dtype=torch.int64), f"synthetic_{i:06d}", 0
-
-
-def set_weight_decay(models):
-    """1-D tensors, biases and `_no_weight_decay` params get weight_decay 0 (utils/optimizer.py:53-77)."""
-    decay, no_decay = [], []
-    for model in models:
-        for name, p in unwrap(model).named_parameters():
-            if not p.requires_grad:
-                continue
-            (no_decay if (p.ndim == 1 or name.endswith(".bias") or getattr(p, "_no_weight_decay", False))
-             else decay).append(p)
-    return [{"params": decay}, {"params": no_decay, "weight_decay": 0.0}]
-
-
-def build_optimizer(config, models, capturable=False):
-    if not isinstance(models, (list, tuple)):
-        models = [models]
-    groups = set_weight_decay(models)
-    name = config.TRAIN.OPTIMIZER.NAME.lower()
-    if name == "adamw":
-        on_gpu = any(p.is_cuda for g in groups for p in g["params"])
-        # capturable: the learning rate is a DEVICE tensor the fused kernel reads at run time, so the schedule keeps
-        # working when the step is replayed from a HIP graph (a CPU tensor is read with .item() at capture and
-        # frozen into the graph); Trainer.lr_to_device() re-establishes this after .to(device) / load_state_dict
-        dev = next((p.device for g in groups for p in g["params"]), torch.device("cpu"))
-        lr = torch.tensor(float(config.TRAIN.BASE_LR), device=dev) if capturable else config.TRAIN.BASE_LR
-        # fused: one multi-tensor kernel per step instead of ~10 foreach passes over 44 M parameters
-        extra = dict(fused=True) if (capturable and on_gpu and knobs.get("VMASR_FUSED_ADAMW")) \
-            else dict(foreach=True if capturable else None)
-        return torch.optim.AdamW(groups, lr=lr, eps=config.TRAIN.OPTIMIZER.EPS,
-                                 betas=tuple(config.TRAIN.OPTIMIZER.BETAS), weight_decay=config.TRAIN.WEIGHT_DECAY,
-                                 capturable=capturable, **extra)
-    if name == "sgd":
-        return torch.optim.SGD(groups, lr=config.TRAIN.BASE_LR, momentum=config.TRAIN.OPTIMIZER.MOMENTUM,
-                               nesterov=True, weight_decay=config.TRAIN.WEIGHT_DECAY)
-    raise NotImplementedError(name)
-
-
-class CosineWarmupScheduler:
-    """Linear warm-up from MIN_LR then one cosine cycle to MIN_LR, stepped per update
-    (`step_update`), like the timm scheduler the reference configures (utils/lr_scheduler.py:15-41)."""
-
-    def __init__(self, optimizer, total_steps, warmup_steps, base_lr, min_lr, warmup_prefix=True):
-        self.opt, self.base_lr, self.min_lr = optimizer, base_lr, min_lr
-        self.warm = max(0, int(warmup_steps))
-        self.t_initial = max(1, int(total_steps - self.warm if warmup_prefix else total_steps))
-        self.prefix = warmup_prefix
-        self.step_update(0)
-
-    def lr_at(self, t):
-        if t < self.warm:
-            return self.min_lr + (self.base_lr - self.min_lr) * t / max(1, self.warm)
-        tt = t - self.warm if self.prefix else t
-        if tt >= self.t_initial:
-            return self.min_lr
-        return self.min_lr + 0.5 * (self.base_lr - self.min_lr) * (1 + math.cos(math.pi * tt / self.t_initial))
-
-    def step_update(self, num_updates):
-        lr, done = self.lr_at(num_updates), set()
-        for g in self.opt.param_groups:
-            if torch.is_tensor(g["lr"]):
-                if g["lr"].data_ptr() not in done:      # capturable optimisers keep ONE lr tensor on the device
-                    g["lr"].fill_(lr)
-                    done.add(g["lr"].data_ptr())
-            else:
-                g["lr"] = lr
-
-
-def lr_to_device(optimizer, device):
-    """Capturable optimisers: every param group shares one lr tensor that lives on `device` (see build_optimizer).
-    Needed after the models moved to the GPU and after `optimizer.load_state_dict` (which restores a CPU value)."""
-    if optimizer is None or not optimizer.defaults.get("capturable", False):
-        return
-    shared = {}
-    for g in optimizer.param_groups:
-        v = float(g["lr"])
-        if v not in shared:
-            shared[v] = torch.tensor(v, dtype=torch.float32, device=device)
-        g["lr"] = shared[v]
-
-
-_RUNTIME_GROUP_KEYS = ("capturable", "fused", "foreach", "differentiable")
-
-
-def portable_optimizer_state(optimizer):
-    """optimizer.state_dict() in the form ANY torch.optim.AdamW accepts — in particular the reference's plain one
-    (main.py:168-201 builds it non-fused, non-capturable, float lr): `lr` as a Python float, the runtime flags of this
-    package's optimisers (capturable / fused / foreach) reset to their defaults, `step` counters as CPU tensors.
-    `load_optimizer_state` below is the inverse for an optimiser built by build_optimizer()."""
-    sd = optimizer.state_dict()
-    groups = []
-    for g in sd["param_groups"]:
-        g = dict(g)
-        g["lr"] = float(g["lr"])
-        if "capturable" in g:
-            g["capturable"] = False
-        for k in ("fused", "foreach"):
-            if k in g:
-                g[k] = None
-        groups.append(g)
-    state = {pid: {k: (v.detach().cpu() if (k == "step" and torch.is_tensor(v)) else v) for k, v in st.items()}
-             for pid, st in sd["state"].items()}
-    return {"state": state, "param_groups": groups}
-
-
-def load_optimizer_state(optimizer, state_dict, device):
-    """optimizer.load_state_dict that keeps THIS optimiser's runtime flags (a checkpoint — ours or the reference's —
-    carries its writer's), puts the step counters where a capturable optimiser needs them and re-creates the shared
-    device learning-rate tensor."""
-    keep = [{k: g[k] for k in _RUNTIME_GROUP_KEYS if k in g} for g in optimizer.param_groups]
-    optimizer.load_state_dict(state_dict)
-    for g, k in zip(optimizer.param_groups, keep):
-        g.update(k)
-    if optimizer.defaults.get("capturable", False):
-        for st in optimizer.state.values():
-            if "step" in st:
-                st["step"] = torch.as_tensor(st["step"], dtype=torch.float32).to(device)
-    lr_to_device(optimizer, device)
-
-
 class _Logger:
     """stderr only: stdout belongs to callers that print machine-readable results (bench.py)."""
 
@@ -262,6 +121,7 @@ class BaseTrainer:
         self.log_dir = config.OUTPUT
         self.epoch_log = {}
         self.do_validation = False
+        self.checkpoint_config = None      # _resume_checkpoint(): the config stored in the generator checkpoint
         # (Trainer resumes at the END of its own constructor, once the models sit on their device: the optimiser
         #  state then loads next to the parameters instead of staying on the host)
         if config.MODEL.RESUME_PATH is not None and resume_now:
@@ -433,17 +293,14 @@ class BaseTrainer:
             raise SystemExit(1)
 
 
-class _StreamWork:
-    """The join handle of a collective issued on a stream of ours: wait() = the current stream waits for its event."""
-
-    def __init__(self, event, device):
-        self.event, self.device = event, device
-
-    def wait(self):
-        torch.cuda.current_stream(self.device).wait_event(self.event)
+def _detach_fmaps(fmaps):
+    """A discriminator's feature maps as constants: the MPD's typed link detaches as a whole, nested lists tensor by tensor."""
+    return fmaps.detach() if hasattr(fmaps, "stacks") else [[f.detach() for f in fs] for fs in fmaps]
 
 
 class Trainer(BaseTrainer):
+    _graph_collectives = None      # (also the class's default: graph_collectives() answers before __init__ has run)
+
     def __init__(self, models, metric_ftns, optimizers, config, device, data_loader_train, data_loader_val=None,
                  lr_schedulers=None, amp=False, gan=False, logger=None, len_epoch=None, dp_mode="flat",
                  amp_scope="generator", step_metrics=False):
@@ -458,6 +315,7 @@ class Trainer(BaseTrainer):
         host read until a line is printed / the epoch ends.  Off: the metrics are evaluated on the PRINT_FREQ steps only."""
         super().__init__(models, metric_ftns, optimizers, config, logger, resume_now=False)
         self.step_metrics = bool(step_metrics)
+        self._metric_names = []
         if self.step_metrics:
             known = {getattr(metric_mod, n): n for n in metric_mod.METRIC_ORDER}
             for met in self.metric_ftns or []:
@@ -469,15 +327,20 @@ class Trainer(BaseTrainer):
         if amp_scope not in ("generator", "step"):
             raise ValueError(f"amp_scope='{amp_scope}'")
         self.amp_scope = amp_scope
-        self._flat, self._flat_params, self._flat_views = {}, {}, {}
         self._acc = max(1, int(config.TRAIN.ACCUMULATION_STEPS))
-        self._gather = self._acc == 1   # fresh grads are packed, not accumulated in place
         self._micro = 0                 # micro-batches seen (gradient accumulation)
-        self._pending = []              # in-flight gradient all-reduces (async work handles)
         self._graphed = None
-        self.time_reduces, self._reduce_events = False, []
-        self._flat_lp = {}
         self.device = device[0] if isinstance(device, (tuple, list)) else device
+        # the flat gradient buffers and their all-reduces; gather: fresh grads are packed, not accumulated in place
+        self.grads = FlatGrads(self.models, self.device, self.world, dp_mode, gather=self._acc == 1)
+        # what later calls fill in (streams and communicators come into being on first use, never here)
+        self._side = None                                     # _side_stream()
+        self._warned_streamk = False                          # _two_streams()
+        self._hip_adamw, self._hip_adamw_failed = None, False     # _hip_adamw_steps()
+        self._step_batch, self._lane_bwd_share = None, None   # enable_graphs(): the example batch's size, the chosen CU share
+        self._graph_collectives = None                        # graph_collectives(): None = as VMASR_GRAPH_COLLECTIVES says
+        self.graph_error, self.graph_variants = None, None    # enable_graphs()
+        self.phase_marks, self._phase_buf = {}, None          # _mark()
         self.data_loader, self.data_loader_val = data_loader_train, data_loader_val
         self.len_epoch = len_epoch if len_epoch is not None else (len(data_loader_train) if data_loader_train is not None else 0)
         self.do_validation = data_loader_val is not None and config.DATA.VALID_SPLIT > 0.0
@@ -491,9 +354,8 @@ class Trainer(BaseTrainer):
         lr_schedulers = lr_schedulers or {}
         self.optimizer_G = optimizers["generator"]
         self.lr_scheduler_G = lr_schedulers.get("generator")
-        if self.gan:
-            self.optimizer_D = optimizers["discriminator"]
-            self.lr_scheduler_D = lr_schedulers.get("discriminator")
+        self.optimizer_D = optimizers["discriminator"] if self.gan else None
+        self.lr_scheduler_D = lr_schedulers.get("discriminator") if self.gan else None
         self._init_losses()
         for k, m in list(self.models.items()):
             if m is not None:
@@ -503,7 +365,7 @@ class Trainer(BaseTrainer):
         elif self.world > 1:
             self._broadcast_state()
         self.global_step = 0
-        for opt in (self.optimizer_G, getattr(self, "optimizer_D", None)):
+        for opt in (self.optimizer_G, self.optimizer_D):
             lr_to_device(opt, self.device)
         self._make_shadows()
         if config.MODEL.RESUME_PATH is not None:
@@ -562,30 +424,24 @@ class Trainer(BaseTrainer):
                 out["l2"] = mse_loss(wave_out, wave_target)
             if "multi_resolution_stft" in cfg.LOSSES.GEN:
                 out["multi_resolution_stft"] = self._get_stft_loss(wave_out, wave_target)
-        if "mpd" in parts and self.gan and "mpd" in cfg.ADVERSARIAL.DISCRIMINATORS:
-            mpd = unwrap(self.models["mpd"])  # weights used as constants: no MPD gradients, no DDP hooks
-            if fake_pass is not None:      # shared fake pass (see _forward_backward): scores / features already there
+        for key in self._d_keys():
+            if key not in parts:
+                continue
+            # The discriminator's weights as constants: no D gradients, no DDP hooks (the reference zeroes this pass' D gradients before
+            # the D loss' backward, trainer/trainer.py:401-426).  fmap_real / fake_pass are the period discriminator's; the MSD's real
+            # pass, then its fake pass, always run here: the third and fourth power iteration of the step.
+            disc, f_real = unwrap(self.models[key]), fmap_real if key == "mpd" else None
+            if key == "mpd" and fake_pass is not None:      # shared fake pass (see _forward_losses): scores / features already there
                 y_gen, fmap_gen = fake_pass
             else:
-                if fmap_real is None:  # the reference recomputes the real-signal features here
+                if f_real is None:      # the reference recomputes the real-signal features here
                     with torch.no_grad():
-                        _, fmap_real = mpd.forward_single(wave_target, detach_weights=True)
-                y_gen, fmap_gen = mpd.forward_single(wave_out, detach_weights=True)
+                        _, f_real = disc.forward_single(wave_target, detach_weights=True)
+                y_gen, fmap_gen = disc.forward_single(wave_out, detach_weights=True)
             if not cfg.ADVERSARIAL.ONLY_FEATURE_LOSS:
-                out["adversarial_mpd"] = self.higi_gan_loss.generator_loss(y_gen)
+                out[f"adversarial_{key}"] = self.higi_gan_loss.generator_loss(y_gen)
             if not cfg.ADVERSARIAL.ONLY_ADVERSARIAL_LOSS:
-                out["features_mpd"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * self.higi_gan_loss.feature_loss(fmap_real, fmap_gen)
-        if "msd" in parts and self._msd:
-            # trainer/trainer.py:401-426.  The weights as constants (the reference's D gradients of this pass are zeroed before
-            # the D loss' backward); the real pass, then the fake pass: the third and fourth power iteration of the step
-            msd = unwrap(self.models["msd"])
-            with torch.no_grad():
-                _, fmap_msd = msd.forward_single(wave_target, detach_weights=True)
-            y_gen, fmap_gen = msd.forward_single(wave_out, detach_weights=True)
-            if not cfg.ADVERSARIAL.ONLY_FEATURE_LOSS:
-                out["adversarial_msd"] = self.higi_gan_loss.generator_loss(y_gen)
-            if not cfg.ADVERSARIAL.ONLY_ADVERSARIAL_LOSS:
-                out["features_msd"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * self.higi_gan_loss.feature_loss(fmap_msd, fmap_gen)
+                out[f"features_{key}"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * self.higi_gan_loss.feature_loss(f_real, fmap_gen)
         return out
 
     def _discriminator_losses(self, wave_out, wave_target):
@@ -596,7 +452,7 @@ class Trainer(BaseTrainer):
             fake = wave_out.detach().float()
             mpd = self.models["mpd"]
             y_real, y_gen, fr, _ = (mpd(wave_target, fake) if isinstance(mpd, DDP) else mpd.forward_pair(wave_target, fake))
-            fmap_real = fr.detach() if hasattr(fr, "stacks") else [[f.detach() for f in fs] for fs in fr]
+            fmap_real = _detach_fmaps(fr)
             d = self.higi_gan_loss.discriminator_loss(y_real, y_gen)
             if self.config.TRAIN.ADVERSARIAL.GAN_LOSS_TYPE == "wgan-gp":
                 # double backward: runs the discriminator on plain (twice differentiable) torch operators
@@ -608,7 +464,6 @@ class Trainer(BaseTrainer):
             out["msd"] = self.higi_gan_loss.discriminator_loss(y_real, y_gen)
         return out, fmap_real
 
-    # ---- flat gradient buffers / single-call all-reduce -------------------------------------
     def _broadcast_state(self):
         """Rank 0's parameters and buffers everywhere (what DDP does at construction)."""
         for m in self.models.values():
@@ -617,154 +472,24 @@ class Trainer(BaseTrainer):
             for t in list(m.parameters()) + list(m.buffers()):
                 dist.broadcast(t.data, src=0)
 
-    def _setup_flat(self, key, optimizer):
-        """After a first backward: give every parameter that received a gradient a view into one
-        flat fp32 buffer (never-used parameters keep grad None, as in the reference)."""
-        model = unwrap(self.models[key])
-        used = [p for p in model.parameters() if p.requires_grad and p.grad is not None]
-        flat = torch.zeros(sum(p.numel() for p in used), dtype=torch.float32, device=self.device)
-        off = 0
-        for p in used:
-            n = p.numel()
-            view = flat[off:off + n].view_as(p)
-            view.copy_(p.grad)
-            p.grad = view
-            off += n
-        self._flat[key] = flat
-        self._flat_params[key] = used
-        self._flat_views[key] = [p.grad for p in used]
-        return flat
+    # ---- the flat gradient buffers' collectives: grad_sync.FlatGrads; what bench.py reads of them ----
+    @property
+    def time_reduces(self):
+        return self.grads.time_reduces
 
-    def _zero_grads(self, key, optimizer):
-        """Before a backward.  With a flat buffer and no gradient accumulation the parameters' grads are
-        dropped so that autograd hands over each gradient tensor as produced (no `grad += g` kernel per
-        parameter: 640 launches a step); _gather_grads() then packs them into the flat buffer."""
-        if key in self._flat:
-            if self._gather:
-                for p in self._flat_params[key]:
-                    p.grad = None
-            else:
-                self._flat[key].zero_()
-        else:
-            optimizer.zero_grad(set_to_none=True)
-
-    def _gather_grads(self, key):
-        """After a backward: multi-tensor copy of the fresh gradients into the flat buffer's views, which
-        become the parameters' .grad again (what the all-reduce and the fused AdamW read)."""
-        if key not in self._flat or not self._gather:
-            return
-        params, views = self._flat_params[key], self._flat_views[key]
-        src, dst = [], []
-        for p, v in zip(params, views):
-            if p.grad is None:
-                v.zero_()
-            else:
-                src.append(p.grad)
-                dst.append(v)
-            p.grad = v
-        torch._foreach_copy_(dst, src)
-
-    def _comm_dtype(self, key):
-        """Wire dtype of `key`'s gradient all-reduce.  VMASR_GRAD_COMM: "fp32" (default: what the reference's DDP sends, so N-rank and
-        1-rank training agree to fp32 rounding) | "mpd-bf16": the period discriminator's 164 MB buffer travels as bf16 (82 MB; the
-        fp32 flat buffer stays the optimiser's input, AdamW's moments and the weights stay fp32 — DDP's bf16 compression hook,
-        SURVEY.md 8(e)), the generator's 9 MB as fp32 | "bf16": both.  The 16-bit wire is a NUMERICS CHANGE (3e-4 ... 9e-4 on the
-        losses of one step) and is opt-in until a multi-GPU run has shown loss parity with the fp32 wire.  RCCL only: gloo is
-        the CPU test backend."""
-        mode = knobs.get("VMASR_GRAD_COMM")
-        if mode not in ("bf16", "mpd-bf16") or self.device.type != "cuda" or dist.get_backend() != "nccl":
-            return torch.float32
-        return torch.bfloat16 if (mode == "bf16" or key != "generator") else torch.float32
-
-    def _reduce_grads(self, key, async_op=False):
-        """ONE all-reduce (mean) per model per step over RCCL/xGMI (generator 9 MB fp32, MPD 82 MB bf16 / 164 MB fp32).
-        async_op: the call returns at once and the collective runs on RCCL's own stream, ordered after the CURRENT stream's work so
-        far — the caller overlaps it with further work and joins it with _wait_reduces() before the optimiser reads the gradients.
-        Capturable (RCCL): inside a stream capture the collective becomes a branch of the graph."""
-        emu = knobs.get("VMASR_GRAD_COMM_EMULATE") if self.world == 1 else None
-        if emu and key in self._flat and (emu == "bf16" or (emu == "mpd-bf16" and key != "generator")):
-            # one rank, no wire: the 16-bit wire's ROUNDING applied to this rank's own gradient (tools/wire_dtype_run.py compares the
-            # loss curves of 200 steps with and without it — the numerics question of the bf16 wire, answerable without a second GPU)
-            flat = self._flat[key]
-            flat.copy_(flat.to(torch.bfloat16))
-            return
-        if self.world > 1 and self.dp_mode == "flat":
-            if key not in self._flat:
-                self._setup_flat(key, None)
-            flat = self._flat[key]
-            if not knobs.get("VMASR_OVERLAP_REDUCE"):
-                async_op = False                    # escape hatch: collectives strictly between the graphs, no overlap
-            avg = dist.get_backend() == "nccl"      # RCCL averages in the collective; gloo has no AVG
-            buf = flat
-            if self._comm_dtype(key) != flat.dtype:
-                lp = self._flat_lp.get(key)
-                if lp is None:                      # (allocated before any capture: GraphedTrainStep's warm-up steps reduce too)
-                    lp = self._flat_lp[key] = torch.empty_like(flat, dtype=self._comm_dtype(key))
-                lp.copy_(flat)
-                buf = lp
-            if getattr(self, "_direct_rccl", None) is not None and (torch.cuda.is_current_stream_capturing()
-                                                                     or knobs.get("VMASR_RCCL_DIRECT")):
-                # RCCL's C API on a stream of its own, forked from the current one (vm_asr_amd/rccl.py: the process group's watchdog
-                # cannot live with captured collectives): a branch of the graph being captured
-                cs, cur = self._comm_stream(), torch.cuda.current_stream(self.device)
-                cs.wait_stream(cur)
-                self._direct_rccl.all_reduce_(buf, avg=True, stream=cs)
-                done = torch.cuda.Event()
-                done.record(cs)
-                self._pending.append((_StreamWork(done, self.device), flat, buf, False))
-                return
-            work = dist.all_reduce(buf, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, async_op=async_op)
-            self._pending.append((work if async_op else None, flat, buf, not avg))
-            if not async_op:
-                self._wait_reduces()
-
-    def _comm_stream(self):
-        if getattr(self, "_comm_st", None) is None:
-            self._comm_st = torch.cuda.Stream(self.device)
-        return self._comm_st
-
-    def enable_direct_rccl(self):
-        """Create this trainer's own RCCL communicator (collective over the process group: every rank calls it, outside any capture)."""
-        if getattr(self, "_direct_rccl", None) is None:
-            from .rccl import RcclComm
-            self._direct_rccl = RcclComm(self.device)
-            self._comm_stream()
-        return self._direct_rccl
-
-    def _wait_reduces(self):
-        """Join the pending collectives.  With `time_reduces` (bench.py, N > 1, collectives between the graphs) an event pair
-        brackets the join on the compute stream: the time between them is what the collectives cost the step AFTER the overlap
-        — the EXPOSED all-reduce time (`reduce_exposed_ms()`).  Inside a capture nothing is timed."""
-        capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
-        timed = getattr(self, "time_reduces", False) and self.device.type == "cuda" and bool(self._pending) and not capturing
-        if timed:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        for work, flat, buf, divide in self._pending:
-            if work is not None:
-                work.wait()                # the current stream waits for the collective (no host block on RCCL)
-            if buf is not flat:
-                flat.copy_(buf)            # bf16 wire buffer -> the optimiser's fp32 gradients
-            if divide:
-                flat.div_(self.world)
-        if timed:
-            e1.record()
-            self._reduce_events.append((e0, e1))
-        self._pending = []
+    @time_reduces.setter
+    def time_reduces(self, on):
+        self.grads.time_reduces = on
 
     def reduce_exposed_ms(self):
-        """Sum of the bracketed join times since the last call (synchronises)."""
-        torch.cuda.synchronize(self.device)
-        ms = sum(a.elapsed_time(b) for a, b in self._reduce_events)
-        self._reduce_events = []
-        return ms
+        return self.grads.reduce_exposed_ms()
 
     # ---- one optimisation step (the unit bench.py times) ------------------------------------
     def _set_deferred_reductions(self):
         """LayerNorm's dgamma / dbeta of a whole backward pass in one launch (layernorm.DEFER_REDUCE): only when no
         parameter gradient is read or accumulated in place before the pass ends — flat gradient buffers, no accumulation."""
         from . import layernorm
-        layernorm.DEFER_REDUCE = (self.device.type == "cuda" and self.dp_mode == "flat" and self._gather
+        layernorm.DEFER_REDUCE = (self.device.type == "cuda" and self.dp_mode == "flat" and self._acc == 1
                                   and knobs.get("VMASR_LN_DEFER"))
         layernorm.reset_uses()
 
@@ -782,7 +507,7 @@ class Trainer(BaseTrainer):
             return False
         if not hip_env.streamk_dp_in_force():
             # hipBLASLt's stream-K GEMMs of two concurrent streams can stop the device for good (vm_asr_amd/hip_env.py)
-            if not getattr(self, "_warned_streamk", False):
+            if not self._warned_streamk:
                 self._warned_streamk = True
                 import warnings
                 warnings.warn("TENSILE_STREAMK_DATA_PARALLEL=1 is not known to be in force: the train step stays on one HIP stream "
@@ -806,9 +531,9 @@ class Trainer(BaseTrainer):
         dims = self.config.MODEL.VSSM.DIMS
         dims = dims[0] if isinstance(dims, (list, tuple)) else dims
         r8 = lambda v: max(8, int(round(v / 8.0)) * 8)      # noqa: E731
-        batch = getattr(self, "_step_batch", None) or self.config.DATA.BATCH_SIZE    # (the batch actually built: enable_graphs() notes it)
+        batch = self._step_batch or self.config.DATA.BATCH_SIZE    # (the batch actually built: enable_graphs() notes it)
         bwd = 1 / 2 if dims >= 32 else (3 / 4 if lanes and batch <= 4 else 5 / 8)
-        share = getattr(self, "_lane_bwd_share", None)       # enable_graphs(): the share the timed captures preferred
+        share = self._lane_bwd_share       # enable_graphs(): the share the timed captures preferred
         if lanes and share is not None:
             bwd = share
         return r8(cus * 3 / 8), r8(cus * bwd)
@@ -834,14 +559,14 @@ class Trainer(BaseTrainer):
         if not knobs.get("VMASR_PHASE_EVENTS"):
             return
         from . import _lib
-        if not hasattr(self, "phase_marks"):
-            self.phase_marks, self._phase_buf = {}, torch.zeros(64, dtype=torch.int64, device=self.device)
+        if self._phase_buf is None:
+            self._phase_buf = torch.zeros(64, dtype=torch.int64, device=self.device)
         slot = self.phase_marks.setdefault(name, len(self.phase_marks))
         st = stream if stream is not None else torch.cuda.current_stream(self.device)   # a chosen stream: by hand, not _lib.call
         _lib.check(_lib.lib().vmasr_mark_time(self._phase_buf.data_ptr() + 8 * slot, st.cuda_stream), "mark_time")
 
     def _side_stream(self):
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         return self._side
 
@@ -882,7 +607,7 @@ class Trainer(BaseTrainer):
                 with torch.cuda.stream(side), step_amp():
                     y_fake, f_fake = mpd.forward_single(wave_d)
                     d_losses = {"mpd": self.higi_gan_loss.discriminator_loss(y_real, y_fake)}
-                    f_real = f_real.detach() if hasattr(f_real, "stacks") else [[f.detach() for f in fs] for fs in f_real]
+                    f_real = _detach_fmaps(f_real)
                     g_side = self._generator_losses(wave_d, wave_target, f_real, fake_pass=(y_fake, f_fake), parts=("mpd",))
                     total_d = sum(d_losses.values()) / acc
                     g_mpd = sum(g_side.values()) / acc if g_side else None
@@ -910,7 +635,7 @@ class Trainer(BaseTrainer):
                         y_real, f_real = mpd.forward_single(wave_target)
                         y_fake, f_fake = mpd.forward_single(wave_out.float())
                         d_losses = {"mpd": self.higi_gan_loss.discriminator_loss(y_real, y_fake)}
-                        f_real = f_real.detach() if hasattr(f_real, "stacks") else [[f.detach() for f in fs] for fs in f_real]
+                        f_real = _detach_fmaps(f_real)
                         g_losses = self._generator_losses(wave_out, wave_target, f_real, fake_pass=(y_fake, f_fake))
                     else:
                         d_losses, fmap_real = self._discriminator_losses(wave_out, wave_target)
@@ -929,27 +654,27 @@ class Trainer(BaseTrainer):
         Runs BEFORE the generator's backward so that the 164 MB MPD all-reduce can overlap the latter."""
         if not self.gan:
             return
-        keys = self._d_keys() if self._msd else ["mpd"]
+        keys = self._d_keys()
         if zero:
             for key in keys:
-                self._zero_grads(key, self.optimizer_D)
+                self.grads.zero(key, self.optimizer_D)
         if st["shared"]:
-            st["total_d"].backward(inputs=self._grad_targets("mpd"), retain_graph=True)
+            st["total_d"].backward(inputs=self.grads.targets("mpd"), retain_graph=True)
         else:
             st["total_d"].backward()
         for key in keys:
-            self._gather_grads(key)
+            self.grads.gather(key)
 
     def _backward_g(self, st, zero=True):
         """Backward of the generator loss — through the (shared) discriminator pass for input gradients only."""
         from . import layernorm
         try:
             if zero:
-                self._zero_grads("generator", self.optimizer_G)
+                self.grads.zero("generator", self.optimizer_G)
             if st["shared"]:
                 from .discriminator import skip_weight_grads
                 with skip_weight_grads():
-                    st["total_g"].backward(inputs=self._grad_targets("generator"))
+                    st["total_g"].backward(inputs=self.grads.targets("generator"))
             else:   # the generator's pass saw the discriminator weights as constants (detach_weights)
                 st["total_g"].backward()
         finally:
@@ -957,7 +682,7 @@ class Trainer(BaseTrainer):
             # any other backward (another trainer, a tester, user code) must not inherit it; an aborted pass' queue is dropped
             layernorm.DEFER_REDUCE = False
             layernorm.reset_uses()
-        self._gather_grads("generator")
+        self.grads.gather("generator")
 
     def _backward_two(self, st, zero=True, reduce=False):
         """The backward passes of the two-stream step, issued in the order that lets them overlap (capture order is replay
@@ -985,18 +710,18 @@ class Trainer(BaseTrainer):
                 # with it the discriminator keeps a queue to itself (r05_lane_trace_gen2_edge.log: 186).
                 side.wait_stream(main)
                 if zero:
-                    self._zero_grads("mpd", self.optimizer_D)
+                    self.grads.zero("mpd", self.optimizer_D)
                 with self._side_cus(), scores_only():                             # (beside the generator's backward)
-                    st["total_d"].backward(inputs=self._grad_targets("mpd"))
-                self._gather_grads("mpd")
+                    st["total_d"].backward(inputs=self.grads.targets("mpd"))
+                self.grads.gather("mpd")
                 self._mark("d_bwd_end", side)
                 if reduce and self.gan:
                     # the MPD all-reduce starts HERE, ordered after the side stream: it runs on RCCL's stream beside whatever is
                     # left of the generator's backward on the main stream (and, captured, as a third branch of the step's graph)
-                    self._reduce_grads("mpd", async_op=True)
+                    self.grads.reduce("mpd", async_op=True)
             main.wait_event(handed)
             if zero:
-                self._zero_grads("generator", self.optimizer_G)
+                self.grads.zero("generator", self.optimizer_G)
             roots, seeds = [], []
             if tw["g_sig"] is not None:
                 roots.append(tw["g_sig"])
@@ -1006,11 +731,11 @@ class Trainer(BaseTrainer):
                 gw.record_stream(main)
                 roots.append(tw["wave_f"])
                 seeds.append(gw)
-            torch.autograd.backward(roots, seeds, inputs=self._grad_targets("generator"))
+            torch.autograd.backward(roots, seeds, inputs=self.grads.targets("generator"))
         finally:
             layernorm.DEFER_REDUCE = False
             layernorm.reset_uses()
-        self._gather_grads("generator")
+        self.grads.gather("generator")
         self._mark("g_bwd_end", main)
         main.wait_stream(side)
         self._mark("join", main)
@@ -1025,8 +750,8 @@ class Trainer(BaseTrainer):
             return
         self._backward_d(st, zero)
         if reduce and self.gan:
-            for key in (self._d_keys() if self._msd else ["mpd"]):
-                self._reduce_grads(key, async_op=True)
+            for key in self._d_keys():
+                self.grads.reduce(key, async_op=True)
         self._backward_g(st, zero)
 
     def _forward_backward(self, wave_input, wave_target, highcut, zero=True):
@@ -1043,11 +768,6 @@ class Trainer(BaseTrainer):
         if self.config.TRAIN.ADVERSARIAL.GAN_LOSS_TYPE == "wgan-gp" or "mpd" not in self.config.TRAIN.ADVERSARIAL.DISCRIMINATORS:
             return False
         return knobs.get("VMASR_SHARE_FAKE_PASS") and hasattr(unwrap(self.models["mpd"]), "_forward_batched")
-
-    def _grad_targets(self, key):
-        if key in self._flat_params:
-            return self._flat_params[key]
-        return [p for p in unwrap(self.models[key]).parameters() if p.requires_grad]
 
     def _mpd_weights_once(self):
         """The reference evaluates every spectrally-normalised MPD weight four times per step (real and
@@ -1100,20 +820,20 @@ class Trainer(BaseTrainer):
         torch step) and the gradients live in the flat buffers; None -> use optimizer.step()."""
         if self.device.type != "cuda" or self.dp_mode != "flat" or not knobs.get("VMASR_HIP_ADAMW"):
             return None
-        cur = getattr(self, "_hip_adamw", None)
+        cur = self._hip_adamw
         if cur is not None and all(f.still_valid() for f in cur):
             return cur
-        if getattr(self, "_hip_adamw_failed", False):
+        if self._hip_adamw_failed:
             return None
         from .fused_adamw import HipAdamWStep
         # every model whose parameters the two optimisers hold needs its flat buffer (the D optimiser holds every listed discriminator)
-        d_keys = self._d_keys() if self._msd else (["mpd"] if self.gan else [])
+        d_keys = self._d_keys()
         opts = [self.optimizer_G] + ([self.optimizer_D] if self.gan else [])
-        if any(k not in self._flat for k in ["generator"] + d_keys):
+        if any(k not in self.grads.flat for k in ["generator"] + d_keys):
             return None
         shadows = {id(src): dst for src, dst in zip(self._shadow_params, self._shadow_dst)}
         try:
-            built = [HipAdamWStep(o, shadows, getattr(self, "_shadow_t", None)) for o in opts]
+            built = [HipAdamWStep(o, shadows, self._shadow_t) for o in opts]
         except ValueError as e:
             if "not initialised" in str(e):
                 return None                       # first step: torch creates the state, the next call builds the table
@@ -1123,10 +843,10 @@ class Trainer(BaseTrainer):
         return built
 
     def _reduce_and_step(self):
-        for key in (self._d_keys() if self._msd else (["mpd"] if self.gan else [])):
-            self._reduce_grads(key, async_op=True)
-        self._reduce_grads("generator", async_op=True)
-        self._wait_reduces()
+        for key in self._d_keys():
+            self.grads.reduce(key, async_op=True)
+        self.grads.reduce("generator", async_op=True)
+        self.grads.wait()
         self._optimizer_steps()
 
     # ---- low-precision shadow weights ----------------------------------------------------------
@@ -1164,7 +884,7 @@ class Trainer(BaseTrainer):
         """bf16 shadows <- fp32 parameters (one multi-tensor copy): after optimizer.step() / load_state_dict."""
         if self._shadow_dst:
             torch._foreach_copy_(self._shadow_dst, self._shadow_src)
-        if getattr(self, "_shadow_t_view", None):
+        if self._shadow_t_view:
             torch._foreach_copy_(self._shadow_t_view, self._shadow_t_src)
 
     def train_step(self, wave_input, wave_target, highcut):
@@ -1182,8 +902,8 @@ class Trainer(BaseTrainer):
         st = self._forward_losses(wave_input, wave_target, highcut)
         self._backward_both(st, zero=first, reduce=last)
         if last:
-            self._reduce_grads("generator", async_op=True)
-            self._wait_reduces()
+            self.grads.reduce("generator", async_op=True)
+            self.grads.wait()
             self._optimizer_steps()
             self.global_step += 1
         return st["wave_out"].detach(), st["logs"]
@@ -1388,7 +1108,7 @@ class Trainer(BaseTrainer):
         """Capture the gradient all-reduces INTO the step's graph (RCCL's C API on a communicator of this trainer, vm_asr_amd/rccl.py)?
         Opt-in (VMASR_GRAPH_COLLECTIVES=1): that path has no process-group watchdog behind it and has not run with more than one
         real rank yet; the default keeps the collectives between the graphs on torch.distributed's communicator."""
-        own = getattr(self, "_graph_collectives", None)
+        own = self._graph_collectives
         return knobs.get("VMASR_GRAPH_COLLECTIVES") if own is None else bool(own)
 
     @staticmethod
@@ -1447,7 +1167,7 @@ class Trainer(BaseTrainer):
             upd = (epoch * num_steps + last_idx) // self._acc
             if self.lr_scheduler_G is not None:
                 self.lr_scheduler_G.step_update(upd)
-            if self.gan and getattr(self, "lr_scheduler_D", None) is not None:
+            if self.gan and self.lr_scheduler_D is not None:
                 self.lr_scheduler_D.step_update(upd)
         self.epoch_log = {k: v / max(1, count) for k, v in sums.items()}
         if acc is not None:
