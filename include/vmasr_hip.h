@@ -375,8 +375,14 @@ typedef struct vmasr_cg_slot {
 } vmasr_cg_slot;
 int vmasr_conv_mfma_supported(int32_t Cin, int32_t Cout, int32_t k, int32_t stride);
 /* The same for one stacked launch of `n` slots over `rows` operand rows (the largest of the layer's input and output row counts):
- * also checks the launchers' slot and 32-bit row-offset bounds (forward, input gradient and weight gradient).  Dispatch on this. */
+ * also checks the launchers' slot and row bounds: 1 only if forward (for Cin = 32 the exact-f32 forward too), input gradient and
+ * weight gradient all accept `rows`.  Dispatch on this. */
 int vmasr_conv_mfma_supported_launch(int32_t Cin, int32_t Cout, int32_t k, int32_t stride, int32_t n, int64_t rows);
+/* Which kernel instantiation a launch takes (read-only; the launchers call the same host function): pass 0 = forward, 1 = input
+ * gradient, 2 = weight gradient; ops 0 = bf16 pairs, 1 = the exact-f32 form (Cin = 32; forward and input gradient).
+ * out = {BM, BN, MF}: the output tile (weight gradient: output channels x (tap, channel) columns) and the MFMA form, 16 = 16x16x32,
+ * 32 = 32x32x16 (exact-f32: 32x32x2).  Depends on the channel counts and on the tuning switches the library read at its first use. */
+int vmasr_conv_mfma_config(int32_t pass, int32_t Cin, int32_t Cout, int32_t ops, int32_t out[3]);
 /* CUs the conv_mfma kernels may occupy from now on (process-wide; 0 = all, the default): launched with fewer workgroups than
  * tiles they loop over the tiles.  Used by the two-stream train step while other kernels run beside them; results do
  * not depend on it. */

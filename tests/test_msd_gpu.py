@@ -17,6 +17,29 @@ K, S, PAD = 41, 4, 20
 CASES = [(2, 128, 128, 4, 1201), (2, 128, 256, 16, 301), (2, 256, 512, 16, 76), (1, 512, 1024, 16, 19), (1, 1024, 1024, 16, 19),
          (2, 16, 32, 16, 76), (2, 16, 16, 4, 5), (2, 16, 16, 4, 2), (2, 16, 16, 4, 1)]
 GATE = 2e-5      # max|got - ref| <= 2e-5 max|ref| per tensor: the MPD convolutions' gate (tests/test_mpd.py)
+# (B, Cin, Cout, groups, L, pad): what the launcher admits beyond the module's own layers (0 <= pad < 41, any per-group (Ci, Co)), at the
+# smallest sizes that reach each path of csrc/gconv1d.hip.  Ci = Cin / groups walks the 4-channel LDS stage's remainders (2, 3 alone; 5,
+# 6, 7, 9 behind full stages; 40: the input gradient's 64-row tile, 40 rows used), Co = Cout / groups the output-channel tiles (1, 3 of
+# 16; 17, 24 of 32; 40 of 64; 72 = 64 + 8: a second, ragged tile).  T = outputs, nq = ceil((L + pad) / 4) = the input gradient's
+# positions per residue; tiles: 128 outputs (forward), 64 outputs (weight gradient's K unit), 64 nq (input gradient).
+EDGE_CASES = [
+    (2, 6, 3, 3, 545, 0),          # pad 0, Ci 2, Co 1, T 127
+    (2, 6, 6, 2, 543, 3),          # pad 3, Ci 3, Co 3, T 128
+    (2, 10, 34, 2, 473, 40),       # pad 40, Ci 5, Co 17, T 129
+    (2, 12, 48, 2, 249, 20),       # pad 20, Ci 6, Co 24, T 63
+    (2, 7, 40, 1, 293, 0),         # pad 0, Ci 7, Co 40, T 64, groups 1
+    (2, 18, 144, 2, 291, 3),       # pad 3, Ci 9, Co 72 (two output-channel tiles, the second of 8 rows), T 65
+    (2, 80, 6, 2, 216, 40),        # pad 40, Ci 40 (input gradient: MT 4, 40 of 64 rows), Co 3, nq 64, T 64
+    (2, 8, 16, 8, 257, 0),         # pad 0, groups = Cin (Ci 1, Co 2), nq 65
+    (2, 5, 17, 1, 236, 20),        # pad 20, Ci 5, Co 17, groups 1, nq 64
+    (2, 12, 80, 2, 255, 3),        # pad 3, Ci 6, Co 40, nq 65
+    (2, 6, 6, 2, 41, 0),           # L + 2 pad == 41: T 1, no padding at all
+    (2, 4, 34, 2, 36, 3),          # T 1, the one window padded on both ends; Ci 2, Co 17
+    (2, 7, 1, 1, 10, 20),          # every window padded on both ends (L 10); Ci 7, Co 1, groups 1
+    (2, 9, 9, 9, 10, 40),          # pad 40, L 10: most windows are all padding; groups = Cin
+    (1, 18, 48, 2, 7, 40),         # one K unit in all (B 1, T 12): the weight gradient has ONE slab; Ci 9, Co 24
+    (3, 128, 256, 16, 8231, 3),    # T 2050 -> 3 x 33 K units over 50 slabs of 2: the last slab has one
+]
 
 _REF = {}
 
@@ -25,15 +48,15 @@ def _problem(case, act):
     """Inputs and the float64 CPU result of one case, computed once and shared (never modified)."""
     key = (case, act)
     if key not in _REF:
-        B, Cin, Cout, G, L = case
-        g = torch.Generator().manual_seed(1000 + CASES.index(case))
+        B, Cin, Cout, G, L, pad = case if len(case) == 6 else case + (PAD,)
+        g = torch.Generator().manual_seed(1000 + CASES.index(case) if len(case) == 5 else 3000 + EDGE_CASES.index(case))
         x = torch.randn(B, Cin, L, generator=g)
         w = torch.randn(Cout, Cin // G, K, generator=g) / (Cin // G * K) ** 0.5
         b = torch.randn(Cout, generator=g)
-        T = (L + 2 * PAD - K) // S + 1
+        T = (L + 2 * pad - K) // S + 1
         gy = torch.randn(B, Cout, T, generator=g)
         x64, w64, b64 = x.double().requires_grad_(), w.double().requires_grad_(), b.double().requires_grad_()
-        y64 = F.conv1d(x64, w64, b64, S, PAD, 1, G)
+        y64 = F.conv1d(x64, w64, b64, S, pad, 1, G)
         if act:
             y64 = F.gelu(y64)
         y64.backward(gy.double())
@@ -56,6 +79,72 @@ def test_gconv1d_vs_float64(case, act):
     close(xd.grad, dx64, GATE, f"dx {case} act={act}")
     close(wd.grad, dw64, GATE, f"dW {case} act={act}")
     close(bd.grad, db64, GATE, f"db {case} act={act}")
+
+
+@pytest.mark.parametrize("act", [True, False])
+@pytest.mark.parametrize("case", EDGE_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_gconv1d_edges_vs_float64(case, act):
+    """test_gconv1d_vs_float64 over EDGE_CASES: the same four comparisons at the same gate, the pad per case."""
+    from vm_asr_amd import msd_ops
+    from vm_asr_amd.msd import _GConv1dFn
+    B, Cin, Cout, G, L, pad = case
+    x, w, b, gy, y64, dx64, dw64, db64 = _problem(case, act)
+    assert msd_ops.gconv1d_supported(Cin, Cout, G, K, S) and msd_ops.gconv1d_supported_launch(Cin, Cout, G, K, S, pad, B, L)
+    xd, wd, bd = (t.cuda().requires_grad_() for t in (x, w, b))
+    y = _GConv1dFn.apply(xd, wd, bd, G, S, pad, act)
+    assert y.shape == y64.shape
+    y.backward(gy.cuda())
+    close(y, y64, GATE, f"y {case} act={act}")
+    close(xd.grad, dx64, GATE, f"dx {case} act={act}")
+    close(wd.grad, dw64, GATE, f"dW {case} act={act}")
+    close(bd.grad, db64, GATE, f"db {case} act={act}")
+
+
+def _slabs(case):
+    """(slabs, K units) of the weight gradient: the slab count read back from the workspace size, S (Cout Ci 41 + Cout) floats."""
+    from vm_asr_amd import _lib
+    B, Cin, Cout, G, L, pad = case
+    nbytes = _lib.lib().vmasr_gconv1d_wgrad_workspace(Cin, Cout, G, K, S, pad, B, L)
+    per = 4 * (Cout * (Cin // G) * K + Cout)
+    assert nbytes > 0 and nbytes % per == 0
+    T = (L + 2 * pad - K) // S + 1
+    return nbytes // per, B * -(-T // 64)
+
+
+def test_edge_cases_reach_one_slab_and_a_short_last_slab():
+    """What EDGE_CASES[-2] and [-1] are in the list for, asserted instead of trusted: one slab; several slabs whose last is short."""
+    assert _slabs(EDGE_CASES[-2]) == (1, 1)
+    slabs, units = _slabs(EDGE_CASES[-1])
+    per = -(-units // slabs)
+    assert slabs > 1 and per > 1 and (slabs - 1) * per < units < slabs * per, (slabs, units, per)
+    # and the tile edges the comments name
+    for case, T in zip(EDGE_CASES[:6], (127, 128, 129, 63, 64, 65)):
+        assert (case[4] + 2 * case[5] - K) // S + 1 == T
+    for case, nq in zip(EDGE_CASES[6:10], (64, 65, 64, 65)):
+        assert -(-(case[4] + case[5]) // S) == nq
+    assert sum(c[5] != PAD for c in EDGE_CASES[:10]) >= 5
+
+
+@pytest.mark.parametrize("case", [EDGE_CASES[2], EDGE_CASES[5], EDGE_CASES[-2], EDGE_CASES[-1]], ids=lambda c: "x".join(map(str, c)))
+def test_gconv1d_optional_outputs(case):
+    """The weight gradient with only dw / only db is bitwise the matching output of the full call (one slab, many slabs, ragged tiles);
+    the forward without a bias against float64, with and without the activation."""
+    from vm_asr_amd import msd_ops
+    B, Cin, Cout, G, L, pad = case
+    x, w, b, gy = (t.cuda() for t in _problem(case, True)[:4])
+    y, pre = msd_ops.gconv1d_fwd(x, w, b, G, S, pad, True)
+    dw, db = msd_ops.gconv1d_wgrad(x, gy, pre, w.shape, G, S, pad)
+    only_w = msd_ops.gconv1d_wgrad(x, gy, pre, w.shape, G, S, pad, want_dw=True, want_db=False)
+    only_b = msd_ops.gconv1d_wgrad(x, gy, pre, w.shape, G, S, pad, want_dw=False, want_db=True)
+    assert only_w[1] is None and torch.equal(only_w[0], dw)
+    assert only_b[0] is None and torch.equal(only_b[1], db)
+    pre64 = F.conv1d(x.cpu().double(), w.cpu().double(), None, S, pad, 1, G)
+    y0, pre0 = msd_ops.gconv1d_fwd(x, w, None, G, S, pad, True)
+    close(pre0, pre64, GATE, f"pre without bias {case}")
+    close(y0, F.gelu(pre64), GATE, f"y without bias {case}")
+    y1, none = msd_ops.gconv1d_fwd(x, w, None, G, S, pad, False)
+    assert none is None
+    close(y1, pre64, GATE, f"linear y without bias {case}")
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[2], CASES[6]], ids=lambda c: "x".join(map(str, c)))

@@ -146,6 +146,7 @@ SYMBOLS = {
     "vmasr_gelu_bwd_split": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "vmasr_conv_mfma_supported": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_conv_mfma_supported_launch": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_int64]),
+    "vmasr_conv_mfma_config": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32)]),
     "vmasr_mark_time": (ctypes.c_int, [c_vp, c_vp]),
     "vmasr_im2col2d_rows": (ctypes.c_int, [c_vp, c_vp] + [c_i32] * 10 + [c_vp, c_i32, c_i32, c_vp]),
     "vmasr_col2im2d_rows": (ctypes.c_int, [c_vp, c_vp] + [c_i32] * 10 + [c_vp, c_i32, c_i32, c_vp]),

@@ -17,6 +17,14 @@ def supported(Cin, Cout, k, stride):
     return bool(_lib.lib().vmasr_conv_mfma_supported(int(Cin), int(Cout), int(k), int(stride)))
 
 
+def config(what, Cin, Cout, f32=False):
+    """(BM, BN, MF): the tile and MFMA form the launch of `what` ("fwd" | "dgrad" | "wgrad") takes for these channel counts (f32: the
+    exact-f32 form) — what the launchers themselves ask (csrc/convgemm.hip cg_config).  No GPU needed."""
+    out = (ctypes.c_int32 * 3)()
+    _lib.check(_lib.lib().vmasr_conv_mfma_config(("fwd", "dgrad", "wgrad").index(what), int(Cin), int(Cout), int(bool(f32)), out), "conv_mfma_config")
+    return tuple(out)
+
+
 _LIMIT = {"cus": 0, "min_channels": 0}
 
 

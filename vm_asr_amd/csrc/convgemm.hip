@@ -391,7 +391,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_nt_kernel(const CgP
         }
     }
     if constexpr (EPI == 2) {
-        if (pr.db && pr.ntaps > 0) {                   // fold the RPI row groups in LDS, then ONE atomic per column and tile
+        if (pr.db) {                                   // fold the RPI row groups in LDS, then ONE atomic per column and tile
+            // (a residue class WITHOUT taps, k < stride, still carries the sign term's gradient; the zero-fill problem has no db)
             __syncthreads();                           // (every thread has left the store loop: the fp32 tile can be overwritten)
             *reinterpret_cast<float4 *>(ct + (tid / C4) * BN + 4 * c4) = dbs;
             __syncthreads();
@@ -700,21 +701,77 @@ int env_conv_mfma() {
     return v;
 }
 
-// 256 x 256 tiles when the output width allows and there are enough of them to fill the chip; VMASR_CONV_TILE=128 forces the small tile
-int cg_launch(CgParams &P, int epi, hipStream_t st, int kid, double bytes) {
+// ---- ONE choice of tile and MFMA form for the launchers and the query (vmasr_conv_mfma_config) -------------------------------------
+struct CgConfig {
+    int BM, BN, MF;
+};
+enum { CG_PASS_FWD = 0, CG_PASS_DGRAD = 1, CG_PASS_WGRAD = 2 };
+
+// The NT kernel's configuration for an output of NB columns whose A rows have CA channels per tap (forward: NB = Cout, CA = Cin; input
+// gradient: NB = Cin, CA = Cout).  ops 1 = the exact-f32 form, `fwd` tells its forward (VMASR_CONV_F32_TILE) from its input gradient.
+CgConfig cg_config_nt(int NB, int CA, int ops, bool fwd) {
+    if (ops) {      // forward 128 x 128 / 4 waves, two workgroups per CU: the layer is as much output-write- as MFMA-bound
+        static const int tile = [] { const char *e = getenv("VMASR_CONV_F32_TILE"); return e ? atoi(e) : 128; }();
+        if (!fwd) return {256, 32, 32};
+        return tile == 256 ? CgConfig{256, 128, 32} : CgConfig{128, 128, 32};
+    }
     const int forced = env_conv_tile();
     // v_mfma_f32_16x16x32_bf16 by default: same cycles per FLOP as 32x32x16, but the chip holds a higher clock on it under load
     // (MI355X_MICROARCH.md, DVFS give-back item 7): 5-9 % less time on the 512 -> 1024 and 1024 -> 1024 layers, forward and dgrad
     // (profiles/r04_convgemm_microbench_v4.log); VMASR_CONV_MFMA=32 selects the 32x32x16 form
-    const int mf = env_conv_mfma();
-    if (P.NB % 256 == 0 && forced != 128)
-        return mf == 16 ? cg_launch_cfg<256, 256, 2, 4, 16>(P, epi, st, kid, bytes) : cg_launch_cfg<256, 256, 2, 4, 32>(P, epi, st, kid, bytes);
+    const int mf = env_conv_mfma() == 16 ? 16 : 32;
+    // 256 x 256 tiles when the output width allows; VMASR_CONV_TILE=128 forces the small tile
+    if (NB % 256 == 0 && forced != 128) return {256, 256, mf};
     // 256 x 128 (per wave 64 x 64): only for the 32-channel input side (K = 160: five K steps) — on the 128 -> 512 layer's dgrad it measured
     // SLOWER than 128 x 128 with two workgroups per CU (317 vs 279 us, profiles/r04_convgemm_microbench_v6_b4.log)
-    if (P.NB % 128 == 0 && P.CA == 32 && forced != 128) return cg_launch_cfg<256, 128, 4, 2, 16>(P, epi, st, kid, bytes);
-    if (P.NB == 32) return cg_launch_cfg<256, 32, 8, 1, 16>(P, epi, st, kid, bytes);                            // per wave 32 x 32 (the 32-channel side)
-    return mf == 16 ? cg_launch_cfg<128, 128, 2, 2, 16>(P, epi, st, kid, bytes) : cg_launch_cfg<128, 128, 2, 2, 32>(P, epi, st, kid, bytes);
+    if (NB % 128 == 0 && CA == 32 && forced != 128) return {256, 128, 16};
+    if (NB == 32) return {256, 32, 16};                                   // per wave 32 x 32 (the 32-channel side)
+    return {128, 128, mf};
 }
+
+// The weight gradient's: BM = output channels, BN = (tap, channel) columns of one tile.
+CgConfig cg_config_wgrad(int Cin, int Cout) {
+    // 256 x 256 / 8 waves when both channel counts allow (with the 16x16x32 MFMA form: 597 -> 504-518 us on the 512 -> 1024 layer, 1 012 -> 945-960 us
+    // on 1024 -> 1024, profiles/r04_convgemm_microbench_v5.log; with the 32x32x16 form it had measured no gain); VMASR_CONV_TILE=128 forces the small tile
+    if (Cout % 256 == 0 && Cin % 256 == 0 && env_conv_tile() != 128) return {256, 256, 16};
+    if (Cin == 32) return {128, 32, 16};                                  // the 32 -> 128 layer: 128 x 32 tiles (one tap's 32 channels)
+    return {128, 128, env_conv_mfma() == 32 ? 32 : 16};
+}
+
+CgConfig cg_config(int pass, int Cin, int Cout, int ops) {
+    if (pass == CG_PASS_WGRAD) return cg_config_wgrad(Cin, Cout);
+    return pass == CG_PASS_FWD ? cg_config_nt(Cout, Cin, ops, true) : cg_config_nt(Cin, Cout, ops, false);
+}
+
+int cg_launch(CgParams &P, int epi, hipStream_t st, int kid, double bytes, int ops = 0, bool fwd = true) {
+    const CgConfig c = cg_config_nt(P.NB, P.CA, ops, fwd);
+    const int key = c.BM * 1000000 + c.BN * 1000 + c.MF;
+    if (ops) {
+        switch (key) {
+            case 256128032: return cg_launch_cfg<256, 128, 4, 2, 32, 1>(P, epi, st, kid, bytes);
+            case 256032032: return cg_launch_cfg<256, 32, 8, 1, 32, 1>(P, epi, st, kid, bytes);
+            default: return cg_launch_cfg<128, 128, 2, 2, 32, 1>(P, epi, st, kid, bytes);
+        }
+    }
+    switch (key) {
+        case 256256016: return cg_launch_cfg<256, 256, 2, 4, 16>(P, epi, st, kid, bytes);
+        case 256256032: return cg_launch_cfg<256, 256, 2, 4, 32>(P, epi, st, kid, bytes);
+        case 256128016: return cg_launch_cfg<256, 128, 4, 2, 16>(P, epi, st, kid, bytes);
+        case 256032016: return cg_launch_cfg<256, 32, 8, 1, 16>(P, epi, st, kid, bytes);
+        case 128128032: return cg_launch_cfg<128, 128, 2, 2, 32>(P, epi, st, kid, bytes);
+        default: return cg_launch_cfg<128, 128, 2, 2, 16>(P, epi, st, kid, bytes);
+    }
+}
+
+// ---- ONE row bound per launcher, shared with the query (vmasr_conv_mfma_supported_launch) -----------------------------------------
+// The kernels form every element offset in 64 bits ((size_t)row * row length); what they keep in 32-bit ints are row indices, per-problem
+// row counts and tile counts.  The bounds below keep rows * (widest operand row) under 2^31 elements, which bounds all of those with
+// room to spare.  The pair form's forward needs no more than the input gradient does; the exact-f32 form counts a row in
+// bf16-units (LDA = 2 CA, KB = 2 k Cin), twice the elements, so ITS forward keeps the 2^30 it was written with.
+int64_t cg_fwd_row_bound(int Cin, int Cout, int k, int ops) { return ((int64_t)1 << (ops ? 30 : 31)) / std::max(Cout, k * Cin); }      // rows_out <
+int64_t cg_dgrad_row_bound(int Cin, int Cout, int k) { return ((int64_t)1 << 31) / std::max(Cin, k * Cout); }                           // rows_in <
+int64_t cg_wgrad_grow_bound(int Cin, int Cout) { return ((int64_t)1 << 31) / std::max(Cout, Cin); }                                     // nseq * H1 <
+int64_t cg_wgrad_xrow_bound(int Cin) { return ((int64_t)1 << 31) / Cin; }                                                                // nseq * H <
 
 }  // namespace
 
@@ -734,8 +791,23 @@ VMASR_EXPORT int vmasr_conv_mfma_supported(int32_t Cin, int32_t Cout, int32_t k,
 VMASR_EXPORT int vmasr_conv_mfma_supported_launch(int32_t Cin, int32_t Cout, int32_t k, int32_t stride, int32_t n, int64_t rows) {
     if (!vmasr_conv_mfma_supported(Cin, Cout, k, stride)) return 0;
     if (n < 1 || n > 8 || n * (stride + 1) > CG_MAXP) return 0;
-    const int64_t widest = std::max<int64_t>(std::max(Cin, Cout), (int64_t)k * std::max(Cin, Cout));
-    return rows >= 1 && rows < (1LL << 31) / widest ? 1 : 0;
+    // `rows` stands for every row count of the layer: all three launchers must accept it — and the exact-f32 forward too where it
+    // can be chosen (Cin = 32, the 32 -> 128 layer)
+    int64_t bound = std::min(cg_fwd_row_bound(Cin, Cout, k, 0), cg_dgrad_row_bound(Cin, Cout, k));
+    bound = std::min(bound, std::min(cg_wgrad_grow_bound(Cin, Cout), cg_wgrad_xrow_bound(Cin)));
+    if (Cin == 32) bound = std::min(bound, cg_fwd_row_bound(Cin, Cout, k, 1));
+    return rows >= 1 && rows < bound ? 1 : 0;
+}
+
+// The tile and MFMA form a launch takes: pass 0 = forward, 1 = input gradient, 2 = weight gradient; ops 0 = bf16 pairs, 1 = the
+// exact-f32 form (Cin = 32, forward and input gradient only).  out = {BM, BN, MF}.  The launchers call the same function.
+VMASR_EXPORT int vmasr_conv_mfma_config(int32_t pass, int32_t Cin, int32_t Cout, int32_t ops, int32_t out[3]) {
+    VMASR_REQUIRE(out && pass >= CG_PASS_FWD && pass <= CG_PASS_WGRAD && (ops == 0 || (ops == 1 && Cin == 32 && pass != CG_PASS_WGRAD)), VMASR_EINVAL,
+                  "conv_mfma_config: pass 0..2, ops 0 or 1 (Cin 32, forward / input gradient), out");
+    VMASR_REQUIRE(vmasr_conv_mfma_supported(Cin, Cout, 1, 1), VMASR_EINVAL, "conv_mfma_config: unsupported channel counts (Cin %d, Cout %d)", Cin, Cout);
+    const CgConfig c = cg_config(pass, Cin, Cout, ops);
+    out[0] = c.BM; out[1] = c.BN; out[2] = c.MF;
+    return VMASR_OK;
 }
 
 namespace {
@@ -757,7 +829,7 @@ int cg_fwd(const vmasr_cg_slot *slots, int32_t n, int32_t Cin, int32_t Cout, int
         VMASR_REQUIRE(!ops || (aligned_to(s.ah, 16) && aligned_to(s.bh, 16)), VMASR_EALIGN, "%s: slot %d: operands must be 16-byte aligned", what, i);
         const int64_t H1 = ((int64_t)s.H + 2 * pad - k) / stride + 1;
         const int64_t M = s.nseq * H1;
-        VMASR_REQUIRE(H1 >= 1 && M <= rows_out && rows_out < (1LL << 30) / std::max(Cout, k * Cin), VMASR_EINVAL,
+        VMASR_REQUIRE(H1 >= 1 && M <= rows_out && rows_out < cg_fwd_row_bound(Cin, Cout, k, ops), VMASR_EINVAL,
                       "%s: slot %d: %lld rows do not fit rows_out %lld (or 32-bit offsets)", what, i, (long long)M, (long long)rows_out);
         CgProb &p = P.prob[i];
         p.ah = (const bf16_t *)s.ah; p.al = (const bf16_t *)s.al; p.bh = (const bf16_t *)s.bh; p.bl = (const bf16_t *)s.bl;
@@ -769,13 +841,8 @@ int cg_fwd(const vmasr_cg_slot *slots, int32_t n, int32_t Cin, int32_t Cout, int
         bytes += (double)s.nseq * s.H * Cin * 4 + (double)Cout * k * Cin * 4 + (double)M * Cout * (act ? 12 : 4);
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (ops) {      // 128 x 128 / 4 waves, two workgroups per CU: the layer is as much output-write- as MFMA-bound
-        VMASR_REQUIRE(Cout % 128 == 0, VMASR_EINVAL, "%s: Cout %% 128", what);
-        static const int tile = [] { const char *e = getenv("VMASR_CONV_F32_TILE"); return e ? atoi(e) : 128; }();
-        if (tile == 256) return cg_launch_cfg<256, 128, 4, 2, 32, 1>(P, act != 0 ? 1 : 0, st, VMASR_K_CONV_MFMA_FWD, bytes);
-        return cg_launch_cfg<128, 128, 2, 2, 32, 1>(P, act != 0 ? 1 : 0, st, VMASR_K_CONV_MFMA_FWD, bytes);
-    }
-    return cg_launch(P, act != 0 ? 1 : 0, st, VMASR_K_CONV_MFMA_FWD, bytes);
+    if (ops) VMASR_REQUIRE(Cout % 128 == 0, VMASR_EINVAL, "%s: Cout %% 128", what);
+    return cg_launch(P, act != 0 ? 1 : 0, st, VMASR_K_CONV_MFMA_FWD, bytes, ops, true);
 }
 }  // namespace
 
@@ -816,7 +883,7 @@ int cg_dgrad(const vmasr_cg_slot *slots, const vmasr_cg_gelu_bwd *epi, const flo
         VMASR_REQUIRE(!epi || (epi[i].pre && epi[i].valid >= 0 && (!epi[i].sgn || gtok)), VMASR_EINVAL,
                       "%s: slot %d: pre-activation missing (or a sign map without the loss gradient)", what, i);
         const int64_t H = s.H, H1 = (H + 2 * pad - k) / stride + 1;
-        VMASR_REQUIRE(H1 >= 1 && s.nseq * H <= rows_in && rows_in < (1LL << 31) / std::max(Cin, k * Cout), VMASR_EINVAL,
+        VMASR_REQUIRE(H1 >= 1 && s.nseq * H <= rows_in && rows_in < cg_dgrad_row_bound(Cin, Cout, k), VMASR_EINVAL,
                       "%s: slot %d: %lld rows do not fit rows_in %lld (or 32-bit offsets)", what, i, (long long)(s.nseq * H), (long long)rows_in);
         auto outputs = [&](CgProb &p) {
             p.c0 = s.c0; p.c1 = nullptr; p.ch = nullptr; p.cl = nullptr; p.bias = nullptr;
@@ -851,13 +918,13 @@ int cg_dgrad(const vmasr_cg_slot *slots, const vmasr_cg_gelu_bwd *epi, const flo
             p.hq_mul = 0; p.hq_add = 0; p.crow_mul = 1; p.crow_add = (int)(s.nseq * H);
             p.ntaps = 0; p.tap0 = 0; p.tap_step = 1; p.dstep = 0;
             p.zero_rows = 0;
+            p.db = nullptr;                                                 // (its rows are zero: nothing to add to the bias gradient)
         }
         bytes += (double)s.nseq * H1 * Cout * 4 + (double)Cout * k * Cin * 4 + (double)s.nseq * H * Cin * 4;
         if (epi) bytes += (double)s.nseq * H * Cin * ((s.c0 && s.ch ? 4.0 : 0.0) + 4.0 + (epi[i].sgn ? 1.0 : 0.0));
     }
     P.nprob = np;
-    if (ops) return cg_launch_cfg<256, 32, 8, 1, 32, 1>(P, 0, static_cast<hipStream_t>(stream), VMASR_K_CONV_MFMA_DGRAD, bytes);
-    return cg_launch(P, epi ? 2 : 0, static_cast<hipStream_t>(stream), VMASR_K_CONV_MFMA_DGRAD, bytes);
+    return cg_launch(P, epi ? 2 : 0, static_cast<hipStream_t>(stream), VMASR_K_CONV_MFMA_DGRAD, bytes, ops, false);
 }
 
 }  // namespace
@@ -886,12 +953,9 @@ VMASR_EXPORT int vmasr_conv_mfma_wgrad(const vmasr_cg_slot *slots, int32_t n, in
     VMASR_REQUIRE(vmasr_conv_mfma_supported(Cin, Cout, k, stride) && splits >= 1 && splits <= 64, VMASR_EINVAL,
                   "conv_mfma_wgrad: unsupported shape (Cin %d, Cout %d, k %d, stride %d, splits %d)", Cin, Cout, k, stride, splits);
     CwParams P = {};
-    const int forced = env_conv_tile(), mf = env_conv_mfma();
-    // 256 x 256 / 8 waves when both channel counts allow (with the 16x16x32 MFMA form: 597 -> 504-518 us on the 512 -> 1024 layer, 1 012 -> 945-960 us
-    // on 1024 -> 1024, profiles/r04_convgemm_microbench_v5.log; with the 32x32x16 form it had measured no gain); VMASR_CONV_TILE=128 forces the small tile
-    const bool big = Cout % 256 == 0 && Cin % 256 == 0 && forced != 128;
-    const bool narrow = Cin == 32;                       // the 32 -> 128 layer: 128 x 32 tiles (one tap's 32 channels)
-    const int T = big ? 256 : 128, TK = narrow ? 32 : T;
+    const CgConfig cfg = cg_config_wgrad(Cin, Cout);
+    const bool big = cfg.BM == 256, narrow = cfg.BN == 32;
+    const int T = cfg.BM, TK = cfg.BN;
     P.nslots = n; P.splits = splits; P.tiles_co = Cout / T; P.tiles_kc = k * Cin / TK;
     P.Cin = Cin; P.Cout = Cout; P.k = k; P.stride = stride; P.pad = pad;
     double bytes = 0;
@@ -899,7 +963,7 @@ VMASR_EXPORT int vmasr_conv_mfma_wgrad(const vmasr_cg_slot *slots, int32_t n, in
         const vmasr_cg_slot &s = slots[i];            // ah/al = g pair, bh/bl = x pair, c0 = dW partials, H = input positions
         VMASR_REQUIRE(s.ah && s.al && s.bh && s.bl && s.c0, VMASR_EINVAL, "conv_mfma_wgrad: null tensor in slot %d", i);
         const int64_t H1 = ((int64_t)s.H + 2 * pad - k) / stride + 1, M = s.nseq * H1;
-        VMASR_REQUIRE(H1 >= 1 && M < (1LL << 31) / std::max(Cout, Cin) && s.nseq * (int64_t)s.H < (1LL << 31) / Cin, VMASR_EINVAL,
+        VMASR_REQUIRE(H1 >= 1 && M < cg_wgrad_grow_bound(Cin, Cout) && s.nseq * (int64_t)s.H < cg_wgrad_xrow_bound(Cin), VMASR_EINVAL,
                       "conv_mfma_wgrad: slot %d too large for 32-bit row offsets", i);
         CwProb &p = P.prob[i];
         p.gh = (const bf16_t *)s.ah; p.gl = (const bf16_t *)s.al; p.xh = (const bf16_t *)s.bh; p.xl = (const bf16_t *)s.bl;
@@ -920,7 +984,7 @@ VMASR_EXPORT int vmasr_conv_mfma_wgrad(const vmasr_cg_slot *slots, int32_t n, in
         VMASR_LAUNCH(VMASR_K_CONV_MFMA_WGRAD, bytes, (conv_mfma_wgrad_kernel<256, 256, 2, 4, 16>), dim3(cg_grid(tiles, smem)), dim3(512), smem, st, P);
     } else if (narrow) {
         VMASR_LAUNCH(VMASR_K_CONV_MFMA_WGRAD, bytes, (conv_mfma_wgrad_kernel<128, 32, 4, 1, 16>), dim3(cg_grid(tiles, 2 * (2 * CW_BR * 256 + 2 * CW_BR * 64))), dim3(256), 2 * (2 * CW_BR * 256 + 2 * CW_BR * 64), st, P);
-    } else if (mf == 32) {
+    } else if (cfg.MF == 32) {
         VMASR_LAUNCH(VMASR_K_CONV_MFMA_WGRAD, bytes, (conv_mfma_wgrad_kernel<128, 128, 2, 2, 32>), dim3(cg_grid(tiles, 2 * 4 * CW_BR * 256)), dim3(256), 2 * 4 * CW_BR * 256, st, P);
     } else {
         VMASR_LAUNCH(VMASR_K_CONV_MFMA_WGRAD, bytes, (conv_mfma_wgrad_kernel<128, 128, 2, 2, 16>), dim3(cg_grid(tiles, 2 * 4 * CW_BR * 256)), dim3(256), 2 * 4 * CW_BR * 256, st, P);
