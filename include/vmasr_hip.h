@@ -732,6 +732,22 @@ int vmasr_stem1d_bwd(const float *gy, const float *x, const float *w, const floa
                      size_t ws_bytes, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad, int32_t act,
                      vmasr_stream_t stream);
 
+/* The stem in the generator's pass, with the feature-matching term of its map folded in (GELU always on; the weights are constants):
+ *   term = coef * sum |y - y_real|,   y_real (B, Cout, T): the real signal's map, any fp32 tensor of y's shape.
+ * _fm_supported_launch: the stem's own admitted set (vmasr_stem1d_supported_launch); both launchers check exactly it.
+ * fm_fwd: writes y, bit-equal to vmasr_stem1d_fwd's (act on), and partials[i] = the i-th workgroup's sum of |y - y_real| in fp64:
+ *         vmasr_stem1d_fm_workspace() bytes (0 for a refused shape), every slot written; the caller adds them (a fixed order, no float
+ *         atomics) and applies coef.  Neither a sign nor a difference tensor is written.
+ * fm_bwd: dx (B, 1, L) alone, from g = gy + coef * gterm[0] * sgn(y - y_real) (sgn(0) = 0) times GELU'(pre), with pre and y rebuilt in
+ *         registers by the forward's own arithmetic.  gterm: DEVICE scalar, the term's upstream gradient (no host read), NULL = none;
+ *         gy NULL = zeros (the gradient arrives through the term alone); at least one of the two.  No dw / db. */
+int vmasr_stem1d_fm_supported_launch(int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+size_t vmasr_stem1d_fm_workspace(int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+int vmasr_stem1d_fm_fwd(const float *x, const float *w, const float *bias, const float *y_real, float *y, double *partials, size_t ws_bytes,
+                        int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
+int vmasr_stem1d_fm_bwd(const float *gy, const float *x, const float *w, const float *bias, const float *y_real, const float *gterm, float coef,
+                        float *dx, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) ---------------------
  * When enabled, every kernel launch of this library is bracketed by two hipEvents
  * recorded on the stream the kernel is launched on; vmasr_prof_collect() waits for the

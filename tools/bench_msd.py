@@ -7,6 +7,8 @@ hold the output.
 
     python tools/bench_msd.py [--batch 4] [--samples 122640] [--rounds 7] [--window-ms 100] [--step] [--out FILE]
     python tools/bench_msd.py --stem [--step] [...]     # the stem at the three scale lengths, B 4 and 8; --step alternates VMASR_MSD_STEM
+    python tools/bench_msd.py --featmatch [--step] [...]  # the generator's MSD pass with its feature-matching loss (profiles/msd_featmatch.md);
+                                                          # --step alternates VMASR_MSD_FEAT
 """
 import argparse
 import json
@@ -118,6 +120,46 @@ def stem_rows(rounds, window_ms, hidden=128):
     return rows
 
 
+def featmatch_rows(batch, samples, rounds, window_ms, hidden=128):
+    """The generator's pass through the MSD (forward_generator: scores + feature-matching loss, backward to the waveform; training mode,
+    so a power iteration per weight as in the trainer) with VMASR_MSD_FEAT at hip and at torch on the same tensors; then one pass per
+    route for its peak of allocated memory above the resident tensors, and the two routes' loss and dx against each other."""
+    from vm_asr_amd.msd import MultiScaleDiscriminator
+    torch.manual_seed(0)
+    D = MultiScaleDiscriminator(hidden=hidden).cuda().train()
+    real = 0.3 * torch.randn(batch, 1, samples, device="cuda")
+    x = (0.3 * torch.randn(batch, 1, samples, device="cuda")).requires_grad_()
+    with torch.no_grad():
+        _, f_real = D.forward_single(real, detach_weights=True)
+
+    def gen_pass(mode):
+        os.environ["VMASR_MSD_FEAT"] = mode
+        scores, loss = D.forward_generator(x, f_real)
+        (2.0 * loss + sum((s ** 2).mean() for s in scores)).backward()
+        g, x.grad = x.grad, None
+        return loss.detach(), g
+
+    row = {"pass": "generator", "B": batch, "hidden": hidden, "T": samples, "maps_MB": round(sum(4.0 * f.numel() for fs in f_real for f in fs) / 1e6, 1)}
+    for route, r in compare({"hip": lambda: gen_pass("hip"), "torch": lambda: gen_pass("torch")}, rounds, window_ms).items():
+        row[f"{route}_ms"], row[f"{route}_min"], row[f"{route}_max"], row[f"{route}_calls"] = r["ms"], r["min"], r["max"], r["calls"]
+    uv = {k: v.clone() for k, v in D.state_dict().items() if k.endswith("._u") or k.endswith("._v")}
+    out = {}
+    for route in ("hip", "torch"):
+        D.load_state_dict(uv, strict=False)        # the same weights for both routes
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out[route] = gen_pass(route)
+        torch.cuda.synchronize()
+        row[f"{route}_peak_MB"] = round((torch.cuda.max_memory_allocated() - base) / 1e6, 1)
+    (lh, gh), (lt, gt) = out["hip"], out["torch"]
+    row["loss_hip"], row["loss_torch"] = lh.item(), lt.item()
+    row["loss_rel_err"] = abs(lh.item() - lt.item()) / abs(lt.item())
+    row["dx_err_of_max"] = ((gh - gt).abs().max() / gt.abs().max()).item()
+    os.environ.pop("VMASR_MSD_FEAT")
+    return [row]
+
+
 def step_ms(batch, samples, rounds, steps=4, knob="VMASR_MSD_CONV"):
     """One trainer; `knob` (VMASR_MSD_CONV, or VMASR_MSD_STEM for the stem alone) is read at every call, so the two routes alternate
     in windows of `steps` steps on the same state."""
@@ -166,14 +208,22 @@ if __name__ == "__main__":
     ap.add_argument("--window-ms", type=float, default=100.0)
     ap.add_argument("--step", action="store_true", help="also time the eager ['mpd', 'msd'] train step, hip and torch alternated")
     ap.add_argument("--stem", action="store_true", help="time the stem (csrc/stem1d.hip) instead of the grouped layers; --step then alternates VMASR_MSD_STEM")
+    ap.add_argument("--featmatch", action="store_true", help="time the generator's MSD pass with its feature-matching loss, VMASR_MSD_FEAT "
+                    "hip and torch alternated, instead of the layers; --step then alternates VMASR_MSD_FEAT")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.featmatch:
+        rows, knob = featmatch_rows(a.batch, a.samples, a.rounds, a.window_ms), "VMASR_MSD_FEAT"
+    elif a.stem:
+        rows, knob = stem_rows(a.rounds, a.window_ms), "VMASR_MSD_STEM"
+    else:
+        rows, knob = layer_rows(a.batch, a.samples, a.rounds, a.window_ms), "VMASR_MSD_CONV"
     res = {"device": torch.cuda.get_device_name(0), "batch": a.batch, "samples": a.samples, "rounds": a.rounds, "window_ms": a.window_ms,
-           "layers": stem_rows(a.rounds, a.window_ms) if a.stem else layer_rows(a.batch, a.samples, a.rounds, a.window_ms)}
+           "layers": rows}
     for r in res["layers"]:
-        print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}), flush=True)
+        print(json.dumps({k: (round(v, 4) if isinstance(v, float) and abs(v) >= 1e-3 else v) for k, v in r.items()}), flush=True)
     if a.step:
-        res["step"] = step_ms(a.batch, a.samples, a.rounds, knob="VMASR_MSD_STEM" if a.stem else "VMASR_MSD_CONV")
+        res["step"] = step_ms(a.batch, a.samples, a.rounds, knob=knob)
         print(json.dumps({"step": {k: {n: round(x, 2) for n, x in v.items()} for k, v in res["step"].items()}}), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

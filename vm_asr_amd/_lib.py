@@ -217,6 +217,10 @@ SYMBOLS = {
     "vmasr_stem1d_bwd_workspace": (c_sz, [c_i32] * 5 + [c_i64]),
     "vmasr_stem1d_fwd": (ctypes.c_int, [c_vp] * 4 + [c_i32] * 2 + [c_i64] + [c_i32] * 4 + [c_vp]),
     "vmasr_stem1d_bwd": (ctypes.c_int, [c_vp] * 8 + [c_sz] + [c_i32] * 2 + [c_i64] + [c_i32] * 4 + [c_vp]),
+    "vmasr_stem1d_fm_supported_launch": (ctypes.c_int, [c_i32] * 5 + [c_i64]),
+    "vmasr_stem1d_fm_workspace": (c_sz, [c_i32] * 5 + [c_i64]),
+    "vmasr_stem1d_fm_fwd": (ctypes.c_int, [c_vp] * 6 + [c_sz] + [c_i32] * 2 + [c_i64] + [c_i32] * 3 + [c_vp]),
+    "vmasr_stem1d_fm_bwd": (ctypes.c_int, [c_vp] * 6 + [ctypes.c_float] + [c_vp] + [c_i32] * 2 + [c_i64] + [c_i32] * 3 + [c_vp]),
     "vmasr_resample_poly": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_resample_design_workspace": (c_sz, [c_i32]),
     "vmasr_resample_design": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),

@@ -21,6 +21,12 @@
 //            fixed order: D_j[t] = sum_o w[o, j] g[o, t] per lane and tap, no exchange inside the channel loop; then
 //            dx[p] = sum_j sum_waves D_j[p + pad - j] through double-buffered LDS rows, once per tile.  Neighbouring tiles recompute
 //            the k - 1 halo positions (the short tile keeps small batches on every CU: 1024-position tiles left half the chip idle).
+//
+// The generator's pass (vmasr_stem1d_fm_fwd / _fm_bwd) folds the feature-matching term of this map, coef sum |y - y_real|, into the same
+// two passes: the forward also reads its tile of y_real and leaves one fp64 partial per workgroup (the caller adds them: a fixed order);
+// the dx kernel rebuilds y beside pre and adds coef * gterm * sgn(y - y_real) to gy before GELU'.  No sign tensor, no difference tensor.
+// The forward and the dx kernel form pre with ONE device function (st_pre), so the y rebuilt there is the forward's y bit for bit: a
+// position where y == y_real has sign 0 in the backward exactly when its |y - y_real| is 0 in the forward.
 #include <algorithm>
 
 #include "common.h"
@@ -52,12 +58,46 @@ __device__ __forceinline__ void st_stage_x(float4 *xq, const float *__restrict__
     }
 }
 
-// grid (ceil(T / 1024), ceil(Cout / 16), B)
+// THE stem arithmetic, defined once: pre = st_pre(acc, bias) with acc[c][i] = sum_{j < k} w_c[j] x[t_i + j - pad] from st_taps, for NC
+// channels at a lane's four positions — a zero-start chain of one fmaf per tap, taps ascending, then the bias in one rounded add.
+// tap(j, c) is w_c[j] (from the kernel's LDS image).
+__device__ __forceinline__ float st_pre(const float acc, const float bv) { return acc + bv; }
+
+template <int NC, class Tap>
+__device__ __forceinline__ void st_taps(float (&pre)[NC][4], const float4 *xr, const int k, const Tap tap) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) pre[c][0] = pre[c][1] = pre[c][2] = pre[c][3] = 0.f;
+    for (int j = 0; j < k; ++j) {
+        const float4 xv = xr[j];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const float wv = tap(j, c);
+            pre[c][0] = fmaf(wv, xv.x, pre[c][0]);
+            pre[c][1] = fmaf(wv, xv.y, pre[c][1]);
+            pre[c][2] = fmaf(wv, xv.z, pre[c][2]);
+            pre[c][3] = fmaf(wv, xv.w, pre[c][3]);
+        }
+    }
+}
+
+// y = GELU(pre) as the ROUNDED fp32 value the forward stores: the empty asm keeps the compiler from contracting gelu_f's last product into
+// a following y - y_real (an fma would see the unrounded product: |y - y| != 0, and a sign where the forward's y ties with y_real)
+__device__ __forceinline__ float st_gelu_rounded(const float pre) {
+    float y = gelu_f(pre);
+    asm volatile("" : "+v"(y));
+    return y;
+}
+
+// grid (ceil(T / 1024), ceil(Cout / 16), B).  FM: also partials[block] = sum over the block's tile of |y - y_real| (fp64; every block
+// writes its own slot, blocks in (b, channel group, tile) order)
+template <bool FM>
 __global__ __launch_bounds__(256) void stem1d_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
-                                                         float *__restrict__ y, const StGeom g) {
+                                                         float *__restrict__ y, const float *__restrict__ y_real,
+                                                         double *__restrict__ partials, const StGeom g) {
     __shared__ float4 xq[4 * kStQ];
     __shared__ __attribute__((aligned(16))) float ws[kStKMax * kStCG];
     __shared__ float bs[kStCG];
+    __shared__ double wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int t0 = blockIdx.x * kStTT, o0 = blockIdx.y * kStCG, b = blockIdx.z;
     const int nch = min(kStCG, g.Cout - o0);
@@ -69,33 +109,38 @@ __global__ __launch_bounds__(256) void stem1d_fwd_kernel(const float *__restrict
     if (tid < kStCG) bs[tid] = (bias && tid < nch) ? bias[o0 + tid] : 0.f;
     __syncthreads();
     float acc[kStCG][4];
-#pragma unroll
-    for (int c = 0; c < kStCG; ++c) acc[c][0] = acc[c][1] = acc[c][2] = acc[c][3] = 0.f;
-    const float4 *xr = xq + wave * kStQ + lane;
-    for (int j = 0; j < g.k; ++j) {
-        const float4 xv = xr[j];
-#pragma unroll
-        for (int c = 0; c < kStCG; ++c) {
-            const float wv = ws[j * kStCG + c];
-            acc[c][0] = fmaf(wv, xv.x, acc[c][0]);
-            acc[c][1] = fmaf(wv, xv.y, acc[c][1]);
-            acc[c][2] = fmaf(wv, xv.z, acc[c][2]);
-            acc[c][3] = fmaf(wv, xv.w, acc[c][3]);
-        }
-    }
+    st_taps(acc, xq + wave * kStQ + lane, g.k, [&](const int j, const int c) { return ws[j * kStCG + c]; });
     const int tl = t0 + wave * 256 + lane;
+    double l1 = 0.0;
 #pragma unroll
     for (int c = 0; c < kStCG; ++c) {
         if (c < nch) {
-            float *yr = y + ((size_t)b * g.Cout + o0 + c) * g.T;
+            const size_t row = ((size_t)b * g.Cout + o0 + c) * g.T;
+            float *yr = y + row;
             const float bv = bs[c];
+            float d[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int t = tl + 64 * i;
-                const float v = acc[c][i] + bv;
-                if (t < g.T) yr[t] = g.act ? gelu_f(v) : v;
+                const float v = st_pre(acc[c][i], bv);
+                if (t < g.T) {
+                    if constexpr (FM) {
+                        const float rv = y_real[row + t], yv = st_gelu_rounded(v);
+                        yr[t] = yv;
+                        d[i] = fabsf(yv - rv);
+                    } else {
+                        yr[t] = g.act ? gelu_f(v) : v;
+                    }
+                }
             }
+            if constexpr (FM) l1 += (double)((d[0] + d[1]) + (d[2] + d[3]));
         }
+    }
+    if constexpr (FM) {                                     // workgroup sum: wave shuffle, then the four waves in order
+        for (int off = 32; off > 0; off >>= 1) l1 += __shfl_down(l1, off, 64);
+        if (lane == 0) wsum[wave] = l1;
+        __syncthreads();
+        if (tid == 0) partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
     }
 }
 
@@ -214,9 +259,13 @@ __global__ __launch_bounds__(256) void stem1d_bwd_reduce_kernel(const float *__r
 
 // grid (ceil(L / (256 - (k - 1))), B).  All four waves work on the SAME 256 gradient positions (4 per lane) and share the channels:
 // wave v takes the sub-chunks of 4 channels with index v mod 4, in ascending order; the four partial D_j are added in wave order.
-template <int KP>
+// FM (act on): the gradient of the map is gy + kc sgn(y - y_real) with y = GELU(pre) rebuilt beside pre, kc = coef * gterm[0] (gterm: the
+// loss term's upstream gradient on the device; NULL: no loss gradient) and sgn(0) = 0; gy may be NULL (zeros).
+template <int KP, bool FM>
 __global__ __launch_bounds__(256) void stem1d_bwd_x_kernel(const float *__restrict__ gy, const float *__restrict__ x, const float *__restrict__ w,
-                                                           const float *__restrict__ bias, float *__restrict__ dx, const StGeom g) {
+                                                           const float *__restrict__ bias, const float *__restrict__ y_real,
+                                                           const float *__restrict__ gterm, const float coef, float *__restrict__ dx,
+                                                           const StGeom g) {
     __shared__ float4 xq[kStQ];
     __shared__ float4 ws4[(kStXC / 4) * KP];                // ws4[sub-chunk][j] = the tap j of its 4 channels
     __shared__ float bs[kStXC];
@@ -232,6 +281,7 @@ __global__ __launch_bounds__(256) void stem1d_bwd_x_kernel(const float *__restri
     const float4 *xr = xq + lane;
     const int tl = tg0 + lane;
     float *wsf = reinterpret_cast<float *>(ws4);
+    const float kc = (FM && gterm) ? coef * gterm[0] : 0.f;
     for (int oc0 = 0; oc0 < g.Cout; oc0 += kStXC) {
         __syncthreads();
         for (int i = tid; i < kStXC * KP; i += 256) {       // i = (sub * KP + j) * 4 + c
@@ -242,38 +292,40 @@ __global__ __launch_bounds__(256) void stem1d_bwd_x_kernel(const float *__restri
         __syncthreads();
         const int nsub = min(kStXC / 4, (g.Cout - oc0 + 3) / 4);
         for (int sub = wave; sub < nsub; sub += 4) {
-            float gv[4][4];
+            float gv[4][4], rv[4][4];
+            unsigned inm = 0;                               // bit 4 c + i: (channel c, position i) lies in the map
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const int o = oc0 + sub * 4 + c;
                 const bool och = o < g.Cout;
-                const float *gr = gy + ((size_t)b * g.Cout + (och ? o : 0)) * g.T;
+                const size_t row = ((size_t)b * g.Cout + (och ? o : 0)) * g.T;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int t = tl + 64 * i;
-                    gv[c][i] = (och && t >= 0 && t < g.T) ? gr[t] : 0.f;
+                    const bool in = och && t >= 0 && t < g.T;
+                    gv[c][i] = (in && (!FM || gy)) ? gy[row + t] : 0.f;
+                    if constexpr (FM) {
+                        rv[c][i] = in ? y_real[row + t] : 0.f;
+                        inm |= (unsigned)in << (4 * c + i);
+                    }
                 }
             }
             const float4 *wr = ws4 + sub * KP;
             if (g.act) {
                 float pre[4][4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) pre[c][0] = pre[c][1] = pre[c][2] = pre[c][3] = bs[sub * 4 + c];
-                for (int j = 0; j < g.k; ++j) {
-                    const float4 xv = xr[j], w4 = wr[j];
-                    const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        pre[c][0] = fmaf(wv[c], xv.x, pre[c][0]);
-                        pre[c][1] = fmaf(wv[c], xv.y, pre[c][1]);
-                        pre[c][2] = fmaf(wv[c], xv.z, pre[c][2]);
-                        pre[c][3] = fmaf(wv[c], xv.w, pre[c][3]);
-                    }
-                }
+                st_taps(pre, xr, g.k, [&](const int j, const int c) { return wsf[(sub * KP + j) * 4 + c]; });
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) gv[c][i] *= gelu_grad_f(pre[c][i]);
+                    for (int i = 0; i < 4; ++i) {
+                        pre[c][i] = st_pre(pre[c][i], bs[sub * 4 + c]);
+                        if constexpr (FM) {                 // outside the map y = GELU(pre) of padding: no sign there
+                            const float yv = st_gelu_rounded(pre[c][i]);
+                            const float sg = ((inm >> (4 * c + i)) & 1u) ? (float)((yv > rv[c][i]) - (yv < rv[c][i])) : 0.f;
+                            gv[c][i] = fmaf(kc, sg, gv[c][i]);
+                        }
+                        gv[c][i] *= gelu_grad_f(pre[c][i]);
+                    }
             }
 #pragma unroll
             for (int j = 0; j < KP; ++j) {                  // zero taps past k
@@ -341,6 +393,34 @@ StSplit st_split(const StGeom &g) {
 
 size_t st_ws_floats(const StGeom &g, const StSplit &s) { return (size_t)s.S * (size_t)g.Cout * (size_t)(g.k + 1); }
 
+dim3 st_fwd_grid(const StGeom &g) { return dim3((unsigned)((g.T + kStTT - 1) / kStTT), (unsigned)((g.Cout + kStCG - 1) / kStCG), (unsigned)g.B); }
+
+size_t st_fm_partials(const StGeom &g) {                   // one fp64 slot per workgroup of the forward
+    const dim3 grid = st_fwd_grid(g);
+    return (size_t)grid.x * grid.y * grid.z;
+}
+
+double st_map_bytes(const StGeom &g) { return 4.0 * (double)g.B * g.Cout * g.T; }
+double st_small_bytes(const StGeom &g) { return 4.0 * ((double)g.B * g.L + (double)g.Cout * (g.k + 1)); }
+
+// the forward and the dx launch, plain (FM false: the last operands unused) and with the feature-matching term
+template <bool FM>
+void st_launch_fwd(const float *x, const float *w, const float *bias, float *y, const float *y_real, double *partials, const StGeom &g,
+                   hipStream_t st) {
+    const dim3 grid = st_fwd_grid(g);
+    const double bytes = st_small_bytes(g) + (FM ? 2.0 : 1.0) * st_map_bytes(g) + (FM ? 8.0 * (double)st_fm_partials(g) : 0.0);
+    VMASR_LAUNCH(VMASR_K_STEM1D_FWD, bytes, stem1d_fwd_kernel<FM>, grid, dim3(256), 0, st, x, w, bias, y, y_real, partials, g);
+}
+
+template <bool FM>
+void st_launch_dx(const float *gy, const float *x, const float *w, const float *bias, const float *y_real, const float *gterm, const float coef,
+                  float *dx, const StGeom &g, hipStream_t st) {
+    const dim3 grid((unsigned)((g.L + (kStXT - g.k)) / (kStXT - (g.k - 1))), (unsigned)g.B);
+    const double bytes = ((gy ? 1.0 : 0.0) + (FM ? 1.0 : 0.0)) * st_map_bytes(g) + st_small_bytes(g) + 4.0 * g.B * g.L;
+    if (g.k <= 16) VMASR_LAUNCH(VMASR_K_STEM1D_BWD, bytes, (stem1d_bwd_x_kernel<16, FM>), grid, dim3(256), 0, st, gy, x, w, bias, y_real, gterm, coef, dx, g);
+    else VMASR_LAUNCH(VMASR_K_STEM1D_BWD, bytes, (stem1d_bwd_x_kernel<32, FM>), grid, dim3(256), 0, st, gy, x, w, bias, y_real, gterm, coef, dx, g);
+}
+
 }  // namespace
 }  // namespace vmasr
 
@@ -371,10 +451,7 @@ VMASR_EXPORT int vmasr_stem1d_fwd(const float *x, const float *w, const float *b
                                   int32_t stride, int32_t pad, int32_t act, vmasr_stream_t stream) {
     VMASR_REQUIRE(x && w && y, VMASR_EINVAL, "stem1d_fwd: null tensor (x, w, y)");
     VMASR_ST_CHECK("stem1d_fwd");
-    const StGeom g = st_geom(Cout, k, pad, B, L, act);
-    const dim3 grid((unsigned)((g.T + kStTT - 1) / kStTT), (unsigned)((Cout + kStCG - 1) / kStCG), (unsigned)B);
-    const double bytes = 4.0 * ((double)B * L + (double)Cout * (k + 1) + (double)B * Cout * g.T);
-    VMASR_LAUNCH(VMASR_K_STEM1D_FWD, bytes, stem1d_fwd_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), x, w, bias, y, g);
+    st_launch_fwd<false>(x, w, bias, y, nullptr, nullptr, st_geom(Cout, k, pad, B, L, act), static_cast<hipStream_t>(stream));
     return check_launch("stem1d_fwd");
 }
 
@@ -385,7 +462,7 @@ VMASR_EXPORT int vmasr_stem1d_bwd(const float *gy, const float *x, const float *
     VMASR_ST_CHECK("stem1d_bwd");
     const StGeom g = st_geom(Cout, k, pad, B, L, act);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const double map = 4.0 * (double)B * Cout * g.T, small = 4.0 * ((double)B * L + (double)Cout * (k + 1));
+    const double map = st_map_bytes(g), small = st_small_bytes(g);
     StSplit s{};
     if (dw || db) {
         s = st_split(g);
@@ -393,11 +470,7 @@ VMASR_EXPORT int vmasr_stem1d_bwd(const float *gy, const float *x, const float *
         VMASR_REQUIRE(ws && ws_bytes >= need && aligned_to(ws, 4), VMASR_EINVAL,
                       "stem1d_bwd: workspace missing, too small or unaligned (%zu bytes, need %zu)", ws_bytes, need);
     }
-    if (dx) {
-        const dim3 grid((unsigned)((L + (kStXT - k)) / (kStXT - (k - 1))), (unsigned)B);
-        if (k <= 16) VMASR_LAUNCH(VMASR_K_STEM1D_BWD, map + small + 4.0 * B * L, stem1d_bwd_x_kernel<16>, grid, dim3(256), 0, st, gy, x, w, bias, dx, g);
-        else VMASR_LAUNCH(VMASR_K_STEM1D_BWD, map + small + 4.0 * B * L, stem1d_bwd_x_kernel<32>, grid, dim3(256), 0, st, gy, x, w, bias, dx, g);
-    }
+    if (dx) st_launch_dx<false>(gy, x, w, bias, nullptr, nullptr, 0.f, dx, g, st);
     if (dw || db) {
         float *part = static_cast<float *>(ws);
         const dim3 grid(s.groups, (unsigned)s.S);
@@ -410,4 +483,36 @@ VMASR_EXPORT int vmasr_stem1d_bwd(const float *gy, const float *x, const float *
                      dim3(256), 0, st, part, dw, db, n, (int)k, s.S);
     }
     return check_launch("stem1d_bwd");
+}
+
+// ---- the generator's pass: the stem with its feature-matching term (GELU always on) --------------------------------------------------
+VMASR_EXPORT int vmasr_stem1d_fm_supported_launch(int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L) {
+    return st_launch_ok(Cout, k, stride, pad, B, L) ? 1 : 0;
+}
+
+VMASR_EXPORT size_t vmasr_stem1d_fm_workspace(int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L) {
+    if (!st_launch_ok(Cout, k, stride, pad, B, L)) return 0;
+    return st_fm_partials(st_geom(Cout, k, pad, B, L, 1)) * sizeof(double);
+}
+
+VMASR_EXPORT int vmasr_stem1d_fm_fwd(const float *x, const float *w, const float *bias, const float *y_real, float *y, double *partials,
+                                     size_t ws_bytes, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad,
+                                     vmasr_stream_t stream) {
+    VMASR_REQUIRE(x && w && y_real && y, VMASR_EINVAL, "stem1d_fm_fwd: null tensor (x, w, y_real, y)");
+    VMASR_ST_CHECK("stem1d_fm_fwd");
+    const StGeom g = st_geom(Cout, k, pad, B, L, 1);
+    const size_t need = st_fm_partials(g) * sizeof(double);
+    VMASR_REQUIRE(partials && ws_bytes >= need && aligned_to(partials, 8), VMASR_EINVAL,
+                  "stem1d_fm_fwd: workspace missing, too small or unaligned (%zu bytes, need %zu)", ws_bytes, need);
+    st_launch_fwd<true>(x, w, bias, y, y_real, partials, g, static_cast<hipStream_t>(stream));
+    return check_launch("stem1d_fm_fwd");
+}
+
+VMASR_EXPORT int vmasr_stem1d_fm_bwd(const float *gy, const float *x, const float *w, const float *bias, const float *y_real, const float *gterm,
+                                     float coef, float *dx, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad,
+                                     vmasr_stream_t stream) {
+    VMASR_REQUIRE(x && w && y_real && dx && (gy || gterm), VMASR_EINVAL, "stem1d_fm_bwd: null tensor (x, w, y_real, dx; one of gy, gterm)");
+    VMASR_ST_CHECK("stem1d_fm_bwd");
+    st_launch_dx<true>(gy, x, w, bias, y_real, gterm, coef, dx, st_geom(Cout, k, pad, B, L, 1), static_cast<hipStream_t>(stream));
+    return check_launch("stem1d_fm_bwd");
 }

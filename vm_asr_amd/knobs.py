@@ -136,6 +136,9 @@ KNOBS = {k.name: k for k in (
        "torch = F.conv1d (A/B measurements, double backward)", values=("hip", "torch"), reader="python:msd"),
     _k("VMASR_MSD_STEM", "choice", "hip", "the MSD's 1 -> hidden stem convolution + GELU: hip = one fused pass that keeps no pre-activation "
        "(csrc/stem1d.hip), torch = F.conv1d + F.gelu (A/B measurements, double backward)", values=("hip", "torch"), reader="python:msd"),
+    _k("VMASR_MSD_FEAT", "choice", "hip", "the MSD's feature-matching loss in the generator's pass: hip = formed on the way (the stem's share inside "
+       "the stem kernels, the other maps in the one-pass L1 kernel; msd_featmatch.py), torch = forward_single + the loop of sub, abs, mean",
+       values=("hip", "torch"), reader="python:msd"),
     # ---- train step
     _k("VMASR_TWO_STREAM", "choice", "1", "the discriminator on a side stream: 1 on, 0 one stream, force also in deterministic mode (test hook)",
        values=("1", "0", "force")),

@@ -17,6 +17,9 @@ How it runs:
     The two remaining dense layers (8h -> 8h k 5, 8h -> 1 k 3) and the pools are torch operators.  VMASR_MSD_CONV=torch routes every
     layer through F.conv1d (A/B measurements; and what discriminator.plain_torch_ops selects: the HIP functions are differentiable
     once); VMASR_MSD_STEM=torch does that for the stem alone.
+  * The generator's pass, forward_generator(x, f_real) -> (scores, feature-matching loss), forms the loss on the way on the GPU
+    (msd_featmatch.py: the stem's share inside the stem kernels, the other maps in the one-pass L1 kernel); VMASR_MSD_FEAT=torch,
+    CPU tensors and plain_torch_ops run forward_single and the reference's loop.
   * The module computes in fp32 with autocast disabled, so amp_scope="step" leaves the MSD in fp32.
   * Spectral norm follows the reference's schedule exactly: one power iteration per training forward of a ScaleDiscriminator, the
     weight normalised anew in every pass (the layers read their parametrization directly, so an enclosing
@@ -123,6 +126,20 @@ def _weight(layer):
     return layer.weight
 
 
+def is_stem(layer):
+    return layer.groups == 1 and layer.in_channels == 1 and layer.stride[0] == 1
+
+
+def conv_layer(x, layer, w, b, act):
+    """One layer of a ScaleDiscriminator with the weight and bias given: the grouped kernels, the stem, or torch's dense convolution."""
+    if layer.groups > 1:
+        return grouped_conv1d(x, w, b, layer.groups, layer.stride[0], layer.padding[0], act)
+    if is_stem(layer):
+        return stem_conv1d(x, w, b, 1, layer.padding[0], act)
+    x = F.conv1d(x, w, b, layer.stride, layer.padding)
+    return F.gelu(x) if act else x
+
+
 class ScaleDiscriminator(nn.Module):
     def __init__(self, use_spectral_norm=False, hidden=128):
         super().__init__()
@@ -150,15 +167,7 @@ class ScaleDiscriminator(nn.Module):
                 w, b = _weight(layer), layer.bias
                 if detach_weights:
                     w, b = w.detach(), b.detach()
-                act = layer is not self.conv_post
-                if layer.groups > 1:
-                    x = grouped_conv1d(x, w, b, layer.groups, layer.stride[0], layer.padding[0], act)
-                elif layer.in_channels == 1 and layer.stride[0] == 1:
-                    x = stem_conv1d(x, w, b, 1, layer.padding[0], act)
-                else:
-                    x = F.conv1d(x, w, b, layer.stride, layer.padding)
-                    if act:
-                        x = F.gelu(x)
+                x = conv_layer(x, layer, w, b, layer is not self.conv_post)
                 fmap.append(x)
         return torch.flatten(x, 1, -1), fmap
 
@@ -199,6 +208,17 @@ class MultiScaleDiscriminator(nn.Module):
         """Scores and feature maps of ONE signal batch (the generator's pass: detach_weights=True uses the weights as constants)."""
         res = [d(a, detach_weights) for d, a in zip(self.discriminators, self._scales(x))]
         return [r[0] for r in res], [r[1] for r in res]
+
+    def forward_generator(self, x, f_real):
+        """The generator's pass: -> (scores of x, the feature-matching loss against the real signal's maps f_real), the weights as
+        constants, the same _weight calls in the same order as forward_single (one power iteration per weight in training mode).
+        On the GPU the loss is formed on the way (msd_featmatch: the stem's share inside the stem kernels, the other maps in the
+        one-pass L1 kernel); CPU tensors, plain_torch_ops and VMASR_MSD_FEAT=torch run forward_single and the reference's loop."""
+        from . import msd_featmatch as fm          # (it imports this module)
+        if fm.fused_ok(x):
+            return fm.feature_matching(f_real, self._scales(x), self.discriminators)
+        scores, fmaps = self.forward_single(x, detach_weights=True)
+        return scores, fm.composed_feature_loss(f_real, fmaps)
 
     def forward_pair(self, y, y_hat):
         """Same results as forward(y, y_hat) from ONE pass over the stacked batch [y; y_hat] (same weights, identical per-sample

@@ -99,3 +99,38 @@ def stem1d_bwd(gy, x, w, bias, pad, act, want_dx=True, want_dw=True, want_db=Tru
     db = _new(x, (Cout,)) if want_db else None
     _call(_lib.lib().vmasr_stem1d_bwd, gy, x, w, bias, dx, dw, db, ws, nbytes, B, Cout, L, k, 1, pad, int(bool(act)))
     return dx, dw, db
+
+
+def stem1d_fm_supported_launch(Cout, k, stride, pad, B, L):
+    """What vmasr_stem1d_fm_fwd / _fm_bwd accept (the same predicate they check): the stem's own set, GELU on."""
+    return bool(_lib.lib().vmasr_stem1d_fm_supported_launch(int(Cout), int(k), int(stride), int(pad), int(B), int(L)))
+
+
+def stem1d_fm_fwd(x, w, bias, y_real, pad):
+    """-> (y, partials): y = GELU(conv1d(x, w, bias, 1, pad)), bit-equal to stem1d_fwd's, and the float64 per-workgroup sums of
+    |y - y_real| (the caller adds them); y_real: y's shape.  Neither a sign nor a difference tensor is written."""
+    B, _, L = x.shape
+    Cout, _, k = w.shape
+    y = _new(x, (B, Cout, out_len(L, k, 1, pad)))
+    if tuple(y_real.shape) != tuple(y.shape):
+        raise RuntimeError(f"stem1d_fm_fwd: y_real {tuple(y_real.shape)} is not the map's shape {tuple(y.shape)}")
+    nbytes = _lib.lib().vmasr_stem1d_fm_workspace(Cout, k, 1, pad, B, L)       # (0: a refused shape; the launcher says which)
+    partials = _new(x, (max(nbytes // 8, 1),), torch.float64)
+    _call(_lib.lib().vmasr_stem1d_fm_fwd, x, w, bias, y_real, y, partials, nbytes, B, Cout, L, k, 1, pad)
+    return y, partials
+
+
+def stem1d_fm_bwd(gy, x, w, bias, y_real, gterm, coef, pad):
+    """-> dx (B, 1, L) from g = gy + coef * gterm * sgn(y - y_real) with y and the pre-activation rebuilt in registers.  gy (the map's
+    upstream gradient) or gterm (the loss term's, ONE fp32 element on the device) may be None, not both; coef: a Python float."""
+    B, _, L = x.shape
+    Cout, _, k = w.shape
+    T = out_len(L, k, 1, pad)
+    for name, t in (("gy", gy), ("y_real", y_real)):
+        if t is not None and tuple(t.shape) != (B, Cout, T):
+            raise RuntimeError(f"stem1d_fm_bwd: {name} {tuple(t.shape)} is not the map's shape {(B, Cout, T)}")
+    if gterm is not None and gterm.numel() != 1:
+        raise RuntimeError("stem1d_fm_bwd: gterm must have one element")
+    dx = _new(x, tuple(x.shape))
+    _call(_lib.lib().vmasr_stem1d_fm_bwd, gy, x, w, bias, y_real, gterm, float(coef), dx, B, Cout, L, k, 1, pad)
+    return dx

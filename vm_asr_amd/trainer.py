@@ -431,17 +431,23 @@ class Trainer(BaseTrainer):
             # the D loss' backward, trainer/trainer.py:401-426).  fmap_real / fake_pass are the period discriminator's; the MSD's real
             # pass, then its fake pass, always run here: the third and fourth power iteration of the step.
             disc, f_real = unwrap(self.models[key]), fmap_real if key == "mpd" else None
+            f_loss = None
             if key == "mpd" and fake_pass is not None:      # shared fake pass (see _forward_losses): scores / features already there
                 y_gen, fmap_gen = fake_pass
             else:
                 if f_real is None:      # the reference recomputes the real-signal features here
                     with torch.no_grad():
                         _, f_real = disc.forward_single(wave_target, detach_weights=True)
-                y_gen, fmap_gen = disc.forward_single(wave_out, detach_weights=True)
+                if key == "msd" and not cfg.ADVERSARIAL.ONLY_ADVERSARIAL_LOSS:      # the MSD forms its feature loss on the way
+                    y_gen, f_loss = disc.forward_generator(wave_out, f_real)
+                else:
+                    y_gen, fmap_gen = disc.forward_single(wave_out, detach_weights=True)
             if not cfg.ADVERSARIAL.ONLY_FEATURE_LOSS:
                 out[f"adversarial_{key}"] = self.higi_gan_loss.generator_loss(y_gen)
             if not cfg.ADVERSARIAL.ONLY_ADVERSARIAL_LOSS:
-                out[f"features_{key}"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * self.higi_gan_loss.feature_loss(f_real, fmap_gen)
+                if f_loss is None:
+                    f_loss = self.higi_gan_loss.feature_loss(f_real, fmap_gen)
+                out[f"features_{key}"] = cfg.ADVERSARIAL.FEATURE_LOSS_LAMBDA * f_loss
         return out
 
     def _discriminator_losses(self, wave_out, wave_target):
