@@ -748,6 +748,44 @@ int vmasr_stem1d_fm_fwd(const float *x, const float *w, const float *bias, const
 int vmasr_stem1d_fm_bwd(const float *gy, const float *x, const float *w, const float *bias, const float *y_real, const float *gterm, float coef,
                         float *dx, int32_t B, int32_t Cout, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
 
+/* ---- the scale discriminator's dense tail: stride-1, groups-1 1-D convolution (vm_asr_amd/csrc/dconv1d.hip;
+ *      model/discriminator.py:239-258: Conv1d(8h, 8h, 5, 1, padding=2) + GELU and conv_post = Conv1d(8h, 1, 3, 1, padding=1)) ----
+ *   y[b, o, t] = bias[o] + sum_{c < Cin} sum_{j < k} w[o, c, j] x[b, c, t + j - pad],   x = 0 outside [0, L)
+ * x (B, Cin, L), w (Cout, Cin, k), y (B, Cout, T) with T = L + 2 pad - k + 1: fp32, contiguous, channel-first.
+ * Exact-fp32 products on the matrix cores (v_mfma_f32_16x16x4_f32), sums in a fixed order, no float atomics: every result is
+ * bit-identical from call to call.  vmasr_dconv1d_supported: groups 1, stride 1, 1 <= k <= 8 (vmasr_dconv1d_max_taps), 1 <= Cin, Cout
+ * <= 65536; _supported_launch adds 0 <= pad < k, 1 <= B <= 65535, max(1, k - 2 pad) <= L <= 2^28, B * ceil(T / 32) <= 2^30 (the weight
+ * gradient's 32-bit count of its K units).  The three launchers check exactly that predicate; anything else is VMASR_EINVAL with
+ * nothing launched, as is a null required pointer.
+ * Short maps leave few output tiles, so the forward and the input gradient cut the summed channels into slabs (_fwd_slabs: how many,
+ * 0 for a refused shape) whose partials a second launch adds in slab order; the weight gradient does the same over (b, t) where it has
+ * few (o, c) tiles.  ws: scratch of the matching _workspace() bytes; 0 bytes (one slab, or a refused shape) = ws may be NULL.
+ * fwd  : bias may be NULL.  act != 0: pre = the convolution + bias (kept for the backward), y = GELU(pre) (exact erf); act == 0: y alone,
+ *        pre may be NULL.
+ * dgrad: dx (B, Cin, L) from gy (B, Cout, T); pre != NULL: gy is first multiplied by GELU'(pre) while it is staged (no such tensor is
+ *        written).  Every element of dx is written.
+ * wgrad: dw (Cout, Cin, k) and / or db (Cout) (either may be NULL) from x and gy (same GELU' rule); each is bitwise what the call for
+ *        both returns.
+ * vmasr_dconv1d_pos_tile / _m_tile / _k_chunk: the largest position tile (shorter maps take 32 or 64), the channels of an M tile and
+ * the channels of one staged K chunk (what the tests size their edge cases by). */
+int32_t vmasr_dconv1d_pos_tile(void);
+int32_t vmasr_dconv1d_m_tile(void);
+int32_t vmasr_dconv1d_k_chunk(void);
+int32_t vmasr_dconv1d_max_taps(void);
+int vmasr_dconv1d_supported(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride);
+int vmasr_dconv1d_supported_launch(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+int32_t vmasr_dconv1d_fwd_slabs(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+size_t vmasr_dconv1d_fwd_workspace(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+size_t vmasr_dconv1d_dgrad_workspace(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+size_t vmasr_dconv1d_wgrad_workspace(int32_t Cin, int32_t Cout, int32_t groups, int32_t k, int32_t stride, int32_t pad, int32_t B, int64_t L);
+int vmasr_dconv1d_fwd(const float *x, const float *w, const float *bias, float *y, float *pre, void *ws, size_t ws_bytes, int32_t B,
+                      int32_t Cin, int32_t Cout, int32_t groups, int64_t L, int32_t k, int32_t stride, int32_t pad, int32_t act,
+                      vmasr_stream_t stream);
+int vmasr_dconv1d_dgrad(const float *gy, const float *pre, const float *w, float *dx, void *ws, size_t ws_bytes, int32_t B, int32_t Cin,
+                        int32_t Cout, int32_t groups, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
+int vmasr_dconv1d_wgrad(const float *x, const float *gy, const float *pre, float *dw, float *db, void *ws, size_t ws_bytes, int32_t B,
+                        int32_t Cin, int32_t Cout, int32_t groups, int64_t L, int32_t k, int32_t stride, int32_t pad, vmasr_stream_t stream);
+
 /* ---- in-library kernel timing (HIP events on the launch stream) ---------------------
  * When enabled, every kernel launch of this library is bracketed by two hipEvents
  * recorded on the stream the kernel is launched on; vmasr_prof_collect() waits for the
@@ -827,6 +865,11 @@ enum {
     VMASR_K_STEM1D_FWD,         /* scale discriminator stem: 1 -> Cout stride-1 convolution + bias + GELU, y only (csrc/stem1d.hip) */
     VMASR_K_STEM1D_BWD,         /* its backward with the pre-activation rebuilt in registers: dx, or per-slab dw / db partials */
     VMASR_K_STEM1D_BWD_REDUCE,  /* the ordered sum of those partials (no float atomics) */
+    VMASR_K_DCONV1D_FWD,        /* scale discriminator tail: dense stride-1 1-D convolution + bias + GELU, exact-f32 MFMA (csrc/dconv1d.hip) */
+    VMASR_K_DCONV1D_DGRAD,      /* its input gradient: the same GEMM on reversed taps, GELU' of the incoming gradient on the fly */
+    VMASR_K_DCONV1D_REDUCE,     /* the ordered sum of their K-slab partials + the epilogue (no float atomics) */
+    VMASR_K_DCONV1D_WGRAD,      /* its weight / bias gradient: whole-K tiles, or (b, t) slabs into a workspace */
+    VMASR_K_DCONV1D_WGRAD_REDUCE, /* the ordered sum of those slabs */
     VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };

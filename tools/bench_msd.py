@@ -1,5 +1,6 @@
 """Times the multi-scale discriminator's grouped convolutions, `hip` (csrc/gconv1d.hip) against `torch` (F.conv1d), its stem (`--stem`:
-csrc/stem1d.hip against F.gelu(F.conv1d), gelu_backward and aten.convolution_backward) and the eager ["mpd", "msd"] train step.  One process, one device.  Every figure compares the two routes in the same call, ALTERNATING them: after
+csrc/stem1d.hip against F.gelu(F.conv1d), gelu_backward and aten.convolution_backward), its dense tail (`--tail`: csrc/dconv1d.hip
+against the same operators) and the eager ["mpd", "msd"] train step.  One process, one device.  Every figure compares the two routes in the same call, ALTERNATING them: after
 warm-up calls of both, `--rounds` rounds of (hip window, torch window); a window is n back-to-back calls between two HIP events, n
 chosen per route so that a window lasts about `--window-ms`; the figure of a window is its time / n.  Reported per route: the median,
 the minimum and the maximum of the windows (the spread: a difference inside it is not one).  profiles/msd.md and profiles/msd_stem.md
@@ -7,6 +8,8 @@ hold the output.
 
     python tools/bench_msd.py [--batch 4] [--samples 122640] [--rounds 7] [--window-ms 100] [--step] [--out FILE]
     python tools/bench_msd.py --stem [--step] [...]     # the stem at the three scale lengths, B 4 and 8; --step alternates VMASR_MSD_STEM
+    python tools/bench_msd.py --tail [--step] [...]     # convs.6 and conv_post at the three map lengths, B 8 and 4 (profiles/msd_tail.md);
+                                                        # --step alternates VMASR_MSD_TAIL
     python tools/bench_msd.py --featmatch [--step] [...]  # the generator's MSD pass with its feature-matching loss (profiles/msd_featmatch.md);
                                                           # --step alternates VMASR_MSD_FEAT
 """
@@ -120,6 +123,50 @@ def stem_rows(rounds, window_ms, hidden=128):
     return rows
 
 
+TAIL_LENGTHS, TAIL_LAYERS = (120, 60, 30), (("convs.6", 8, 5, 2, True), ("conv_post", 0, 3, 1, False))
+F32_MATRIX_PEAK_TFLOPS = 157.3      # MI355X, dense fp32 matrix (v_mfma_f32_16x16x4_f32: 256 FLOP / cycle / CU, 256 CUs, 2.4 GHz)
+
+
+def tail_rows(rounds, window_ms, hidden=128):
+    """The dense tail (8h -> 8h k 5 + GELU; conv_post 8h -> 1 k 3) at the workload's map lengths: B 8 (the discriminator's stacked
+    pass: forward, dgrad, wgrad) and B 4 (the generator's pass: forward, dgrad).  pct_peak: the hip route's share of the fp32 matrix peak."""
+    from vm_asr_amd import msd_ops
+    g_in, rows, C = torch.ops.aten.gelu_backward, [], 8 * hidden
+    for name, co_mul, k, pad, act in TAIL_LAYERS:
+        co = co_mul * hidden or 1
+        for batch, op_names in ((8, ("fwd", "dgrad", "wgrad")), (4, ("fwd", "dgrad"))):
+            for L in TAIL_LENGTHS:
+                x = torch.randn(batch, C, L, device="cuda")
+                w = torch.randn(co, C, k, device="cuda") / (C * k) ** 0.5
+                b = torch.randn(co, device="cuda")
+                gy = torch.randn(batch, co, L, device="cuda")
+                pre = msd_ops.dconv1d_fwd(x, w, b, 1, pad, act)[1]
+
+                def cb(mask):
+                    return torch.ops.aten.convolution_backward(g_in(gy, pre) if act else gy, x, w, [co], [1], [pad], [1], False, [0], 1, mask)
+                ops = {
+                    "fwd": {"hip": lambda: msd_ops.dconv1d_fwd(x, w, b, 1, pad, act),
+                            "torch": (lambda: F.gelu(F.conv1d(x, w, b, 1, pad))) if act else (lambda: F.conv1d(x, w, b, 1, pad))},
+                    "dgrad": {"hip": lambda: msd_ops.dconv1d_dgrad(gy, pre, w, x.shape, 1, pad), "torch": lambda: cb([True, False, False])},
+                    "wgrad": {"hip": lambda: msd_ops.dconv1d_wgrad(x, gy, pre, w.shape, 1, pad), "torch": lambda: cb([False, True, True])},
+                }
+                gflop = 2.0 * batch * co * L * C * k / 1e9
+                row = {"layer": name, "B": batch, "Cin": C, "Cout": co, "L": L, "k": k, "gflop": round(gflop, 3)}
+                for op in op_names:
+                    for route, r in compare(ops[op], rounds, window_ms).items():
+                        row[f"{route}_{op}_ms"], row[f"{route}_{op}_min"], row[f"{route}_{op}_max"] = r["ms"], r["min"], r["max"]
+                        row[f"{route}_{op}_calls"] = r["calls"]
+                    row[f"hip_{op}_pct_peak"] = round(100.0 * gflop / row[f"hip_{op}_ms"] / F32_MATRIX_PEAK_TFLOPS, 2)
+                rows.append(row)
+                del x, w, b, gy, pre
+    tot = {r: sum(v for row in rows for n, v in row.items() if n.startswith(r + "_") and n.endswith("_ms")) for r in ("hip", "torch")}
+    spread = {r: sum(row[n[:-3] + "_max"] - row[n[:-3] + "_min"] for row in rows for n in row if n.startswith(r + "_") and n.endswith("_ms"))
+              for r in ("hip", "torch")}
+    rows.append({"layer": "sum of the medians", "hip_ms": tot["hip"], "torch_ms": tot["torch"], "hip_spread_ms": spread["hip"],
+                 "torch_spread_ms": spread["torch"]})
+    return rows
+
+
 def featmatch_rows(batch, samples, rounds, window_ms, hidden=128):
     """The generator's pass through the MSD (forward_generator: scores + feature-matching loss, backward to the waveform; training mode,
     so a power iteration per weight as in the trainer) with VMASR_MSD_FEAT at hip and at torch on the same tensors; then one pass per
@@ -161,7 +208,7 @@ def featmatch_rows(batch, samples, rounds, window_ms, hidden=128):
 
 
 def step_ms(batch, samples, rounds, steps=4, knob="VMASR_MSD_CONV"):
-    """One trainer; `knob` (VMASR_MSD_CONV, or VMASR_MSD_STEM for the stem alone) is read at every call, so the two routes alternate
+    """One trainer; `knob` (VMASR_MSD_CONV, or VMASR_MSD_STEM / VMASR_MSD_TAIL for the stem / the dense tail alone) is read at every call, so the two routes alternate
     in windows of `steps` steps on the same state."""
     from vm_asr_amd import get_model
     from vm_asr_amd.config import get_default_config, update_config
@@ -208,12 +255,15 @@ if __name__ == "__main__":
     ap.add_argument("--window-ms", type=float, default=100.0)
     ap.add_argument("--step", action="store_true", help="also time the eager ['mpd', 'msd'] train step, hip and torch alternated")
     ap.add_argument("--stem", action="store_true", help="time the stem (csrc/stem1d.hip) instead of the grouped layers; --step then alternates VMASR_MSD_STEM")
+    ap.add_argument("--tail", action="store_true", help="time the dense tail (csrc/dconv1d.hip) instead of the grouped layers; --step then alternates VMASR_MSD_TAIL")
     ap.add_argument("--featmatch", action="store_true", help="time the generator's MSD pass with its feature-matching loss, VMASR_MSD_FEAT "
                     "hip and torch alternated, instead of the layers; --step then alternates VMASR_MSD_FEAT")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.featmatch:
         rows, knob = featmatch_rows(a.batch, a.samples, a.rounds, a.window_ms), "VMASR_MSD_FEAT"
+    elif a.tail:
+        rows, knob = tail_rows(a.rounds, a.window_ms), "VMASR_MSD_TAIL"
     elif a.stem:
         rows, knob = stem_rows(a.rounds, a.window_ms), "VMASR_MSD_STEM"
     else:

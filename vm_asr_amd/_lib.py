@@ -210,6 +210,19 @@ SYMBOLS = {
     "vmasr_gconv1d_fwd": (ctypes.c_int, [c_vp] * 5 + [c_i32] * 4 + [c_i64] + [c_i32] * 4 + [c_vp]),
     "vmasr_gconv1d_dgrad": (ctypes.c_int, [c_vp] * 4 + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
     "vmasr_gconv1d_wgrad": (ctypes.c_int, [c_vp] * 6 + [c_sz] + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
+    "vmasr_dconv1d_pos_tile": (c_i32, []),
+    "vmasr_dconv1d_m_tile": (c_i32, []),
+    "vmasr_dconv1d_k_chunk": (c_i32, []),
+    "vmasr_dconv1d_max_taps": (c_i32, []),
+    "vmasr_dconv1d_supported": (ctypes.c_int, [c_i32] * 5),
+    "vmasr_dconv1d_supported_launch": (ctypes.c_int, [c_i32] * 7 + [c_i64]),
+    "vmasr_dconv1d_fwd_slabs": (c_i32, [c_i32] * 7 + [c_i64]),
+    "vmasr_dconv1d_fwd_workspace": (c_sz, [c_i32] * 7 + [c_i64]),
+    "vmasr_dconv1d_dgrad_workspace": (c_sz, [c_i32] * 7 + [c_i64]),
+    "vmasr_dconv1d_wgrad_workspace": (c_sz, [c_i32] * 7 + [c_i64]),
+    "vmasr_dconv1d_fwd": (ctypes.c_int, [c_vp] * 6 + [c_sz] + [c_i32] * 4 + [c_i64] + [c_i32] * 4 + [c_vp]),
+    "vmasr_dconv1d_dgrad": (ctypes.c_int, [c_vp] * 5 + [c_sz] + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
+    "vmasr_dconv1d_wgrad": (ctypes.c_int, [c_vp] * 6 + [c_sz] + [c_i32] * 4 + [c_i64] + [c_i32] * 3 + [c_vp]),
     "vmasr_stem1d_time_tile": (c_i32, []),
     "vmasr_stem1d_channel_group": (c_i32, []),
     "vmasr_stem1d_supported": (ctypes.c_int, [c_i32] * 4),
@@ -346,7 +359,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 73
+K_COUNT = 78
 
 
 def zeros_f32(device, *shapes):

@@ -40,7 +40,8 @@ const char *kNames[VMASR_K_COUNT] = {
     "ss2d_deep_xproj", "ss2d_deep_fwd", "ss2d_deep_bwd", "ss2d_deep_xbwd", "outproj_fwd", "outproj_bwd", "stft_loss",
     "conv_mfma_fwd", "conv_mfma_dgrad", "conv_mfma_wgrad", "wgrad_finish", "skinny_linear", "metrics", "resample_design", "degrade_batch",
     "gconv1d_fwd", "gconv1d_dgrad", "gconv1d_wgrad", "gconv1d_wgrad_reduce",
-    "stem1d_fwd", "stem1d_bwd", "stem1d_bwd_reduce", "resample_poly"};
+    "stem1d_fwd", "stem1d_bwd", "stem1d_bwd_reduce",
+    "dconv1d_fwd", "dconv1d_dgrad", "dconv1d_reduce", "dconv1d_wgrad", "dconv1d_wgrad_reduce", "resample_poly"};
 }  // namespace
 
 bool g_prof_on = false;

@@ -4,7 +4,7 @@
 outside the declared set raises ValueError at the read.  Nothing else under vm_asr_amd/ reads a VMASR_* variable.  Readers:
 "python" = this package through get(), for the switches that existed when this registry was written: tests/test_knobs.py pins exactly
 that set and its defaults in a fixed table.  A python-read switch added later cannot join the table, so it carries "python:<feature>"
-(so far "python:msd") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py);
+(so far "python:msd") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py, tests/test_msd_tail.py);
 "csrc" = a static `getenv` in vm_asr_amd/csrc (read once per process; listed here with the
 default the C++ code applies); "external" = bench.py, the tests, tools/ or oracle/, which read their own names directly.
 No torch import: tests/test_knobs.py and tools load this module without a GPU stack.
@@ -139,6 +139,9 @@ KNOBS = {k.name: k for k in (
     _k("VMASR_MSD_FEAT", "choice", "hip", "the MSD's feature-matching loss in the generator's pass: hip = formed on the way (the stem's share inside "
        "the stem kernels, the other maps in the one-pass L1 kernel; msd_featmatch.py), torch = forward_single + the loop of sub, abs, mean",
        values=("hip", "torch"), reader="python:msd"),
+    _k("VMASR_MSD_TAIL", "choice", "torch", "the MSD's dense tail (8h -> 8h k 5 + GELU, conv_post): hip = the exact-fp32 MFMA kernels with ordered "
+       "split-K sums (csrc/dconv1d.hip: bit-identical run to run, no library algorithm search), torch = F.conv1d + F.gelu (the default: "
+       "faster on the 8h -> 8h layer, profiles/msd_tail.md; double backward)", values=("hip", "torch"), reader="python:msd"),
     # ---- train step
     _k("VMASR_TWO_STREAM", "choice", "1", "the discriminator on a side stream: 1 on, 0 one stream, force also in deterministic mode (test hook)",
        values=("1", "0", "force")),

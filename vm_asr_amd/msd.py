@@ -14,9 +14,14 @@ How it runs:
     ordered sum (bit-identical from run to run).  The stem (1 -> h, k 15, stride 1: the one layer at the waveform rate, the largest
     map of the module) runs on csrc/stem1d.hip: convolution + bias + GELU in one pass that writes y only; its backward rebuilds the
     pre-activation in registers from x, w and bias, so nothing of the map's size is kept for it, and its dw / db are ordered sums too.
-    The two remaining dense layers (8h -> 8h k 5, 8h -> 1 k 3) and the pools are torch operators.  VMASR_MSD_CONV=torch routes every
-    layer through F.conv1d (A/B measurements; and what discriminator.plain_torch_ops selects: the HIP functions are differentiable
-    once); VMASR_MSD_STEM=torch does that for the stem alone.
+    The dense tail (8h -> 8h k 5 + GELU, conv_post 8h -> 1 k 3) has HIP kernels too, csrc/dconv1d.hip, selected by
+    VMASR_MSD_TAIL=hip (the default is torch: the library's convolution is faster on the 8h -> 8h layer, profiles/msd_tail.md): the
+    same exact-fp32 MFMA arithmetic on stride-1 windows, the summed channels cut into slabs whose partials are added in slab order (the maps are too short for output
+    tiles alone to fill the device), the input gradient as the same GEMM on reversed taps, GELU' formed while the gradient is staged:
+    bit-identical from run to run like the other layers, and no library algorithm search in the module.  The pools are ATen operators.
+    VMASR_MSD_CONV=torch routes every layer through F.conv1d (A/B measurements; and what discriminator.plain_torch_ops selects: the
+    HIP functions are differentiable once); VMASR_MSD_STEM=torch does that for the stem alone; VMASR_MSD_TAIL [torch] | hip selects
+    the dense tail's route alone.
   * The generator's pass, forward_generator(x, f_real) -> (scores, feature-matching loss), forms the loss on the way on the GPU
     (msd_featmatch.py: the stem's share inside the stem kernels, the other maps in the one-pass L1 kernel); VMASR_MSD_FEAT=torch,
     CPU tensors and plain_torch_ops run forward_single and the reference's loop.
@@ -34,7 +39,7 @@ from torch.nn.utils.parametrizations import weight_norm
 from . import knobs, msd_ops as bind
 from .discriminator import _PLAIN_OPS, _SpectralNorm, spectral_norm
 
-__all__ = ["ScaleDiscriminator", "MultiScaleDiscriminator", "grouped_conv1d", "stem_conv1d"]
+__all__ = ["ScaleDiscriminator", "MultiScaleDiscriminator", "grouped_conv1d", "stem_conv1d", "dense_conv1d"]
 
 
 class _GConv1dFn(torch.autograd.Function):
@@ -81,6 +86,29 @@ class _Stem1dFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+class _DConv1dFn(torch.autograd.Function):
+    """y = [GELU](conv1d(x, w, bias, 1, pad)) of a dense layer on csrc/dconv1d.hip; saves x, w and the pre-activation."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, pad, act):
+        x, w = x.contiguous(), w.contiguous()
+        y, pre = bind.dconv1d_fwd(x, w, None if bias is None else bias.contiguous(), 1, pad, act)
+        ctx.save_for_backward(x, w, pre)
+        ctx.geom = (pad, bias is not None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w, pre = ctx.saved_tensors
+        pad, has_bias = ctx.geom
+        gy = gy.contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        dx = bind.dconv1d_dgrad(gy, pre, w, x.shape, 1, pad) if need_x else None
+        dw, db = bind.dconv1d_wgrad(x, gy, pre, w.shape, 1, pad, need_w, need_b)
+        return dx, dw, db, None, None
+
+
 def _stem_ok(x, w, bias, stride, pad):
     if not x.is_cuda or _PLAIN_OPS[0] or knobs.get("VMASR_MSD_CONV") != "hip" or knobs.get("VMASR_MSD_STEM") != "hip":
         return False
@@ -119,6 +147,26 @@ def grouped_conv1d(x, w, bias, groups, stride, pad, act):
     return F.gelu(y) if act else y
 
 
+def _dense_ok(x, w, bias, stride, pad):
+    if not x.is_cuda or _PLAIN_OPS[0] or knobs.get("VMASR_MSD_CONV") != "hip" or knobs.get("VMASR_MSD_TAIL") != "hip":
+        return False
+    if any(t.dtype != torch.float32 or not t.is_cuda for t in (x, w) + (() if bias is None else (bias,))):
+        return False
+    if x.dim() != 3 or w.dim() != 3 or w.shape[1] != x.shape[1]:
+        return False
+    return bind.dconv1d_supported_launch(x.shape[1], w.shape[0], 1, w.shape[2], stride, pad, x.shape[0], x.shape[2])
+
+
+def dense_conv1d(x, w, bias, stride, pad, act):
+    """[GELU](F.conv1d(x, w, bias, stride, pad)) of a dense (groups 1) layer: the HIP kernels where vmasr_dconv1d_supported_launch accepts
+    the call (stride 1, k <= 8; fp32 on the GPU, VMASR_MSD_CONV=hip, VMASR_MSD_TAIL=hip, plain_torch_ops off), torch's operators
+    otherwise."""
+    if _dense_ok(x, w, bias, stride, pad):
+        return _DConv1dFn.apply(x, w, bias, pad, act)
+    y = F.conv1d(x, w, bias, stride, pad)
+    return F.gelu(y) if act else y
+
+
 def _weight(layer):
     """The layer's (normalised) weight, evaluated now: one power iteration in training mode, as every reference forward does."""
     if parametrize.is_parametrized(layer, "weight"):
@@ -131,13 +179,12 @@ def is_stem(layer):
 
 
 def conv_layer(x, layer, w, b, act):
-    """One layer of a ScaleDiscriminator with the weight and bias given: the grouped kernels, the stem, or torch's dense convolution."""
+    """One layer of a ScaleDiscriminator with the weight and bias given: the grouped kernels, the stem, or the dense kernels."""
     if layer.groups > 1:
         return grouped_conv1d(x, w, b, layer.groups, layer.stride[0], layer.padding[0], act)
     if is_stem(layer):
         return stem_conv1d(x, w, b, 1, layer.padding[0], act)
-    x = F.conv1d(x, w, b, layer.stride, layer.padding)
-    return F.gelu(x) if act else x
+    return dense_conv1d(x, w, b, layer.stride[0], layer.padding[0], act)
 
 
 class ScaleDiscriminator(nn.Module):

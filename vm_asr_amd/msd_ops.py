@@ -1,5 +1,5 @@
-"""The scale discriminator's HIP entry points (include/vmasr_hip.h, csrc/gconv1d.hip, csrc/stem1d.hip), one Python function each — the
-companion of mpd_ops.py.
+"""The scale discriminator's HIP entry points (include/vmasr_hip.h, csrc/gconv1d.hip, csrc/stem1d.hip, csrc/dconv1d.hip), one Python
+function each — the companion of mpd_ops.py.
 
 Every function takes tensors and plain numbers, allocates its outputs and launches through _lib.call.  No autograd and no switches here:
 vm_asr_amd/msd.py decides what runs.  Layout: channel-first fp32, x (B, Cin, L), w (Cout, Cin / groups, k), y (B, Cout, T); the stem has Cin = groups = stride = 1."""
@@ -54,6 +54,68 @@ def gconv1d_wgrad(x, gy, pre, w_shape, groups, stride, pad, want_dw=True, want_d
     dw = _new(x, tuple(w_shape)) if want_dw else None
     db = _new(x, (Cout,)) if want_db else None
     _call(_lib.lib().vmasr_gconv1d_wgrad, x, gy, pre, dw, db, ws, nbytes, B, Cin, Cout, groups, L, k, stride, pad)
+    return dw, db
+
+
+def dconv1d_tiles():
+    """(largest position tile, channels of an M tile, channels of a staged K chunk, most taps) of csrc/dconv1d.hip (the tests size their
+    edge cases by them)."""
+    l = _lib.lib()
+    return int(l.vmasr_dconv1d_pos_tile()), int(l.vmasr_dconv1d_m_tile()), int(l.vmasr_dconv1d_k_chunk()), int(l.vmasr_dconv1d_max_taps())
+
+
+def dconv1d_supported(Cin, Cout, groups, k, stride):
+    return bool(_lib.lib().vmasr_dconv1d_supported(int(Cin), int(Cout), int(groups), int(k), int(stride)))
+
+
+def dconv1d_supported_launch(Cin, Cout, groups, k, stride, pad, B, L):
+    """What the three dense launchers accept (the same predicate they check): groups 1, stride 1, k <= 8, 0 <= pad < k, B and L within
+    one launch."""
+    return bool(_lib.lib().vmasr_dconv1d_supported_launch(int(Cin), int(Cout), int(groups), int(k), int(stride), int(pad), int(B), int(L)))
+
+
+def dconv1d_fwd_slabs(Cin, Cout, groups, k, stride, pad, B, L):
+    """K slabs of the forward at this shape (1: the epilogue in the GEMM's own launch; 0: a refused shape)."""
+    return int(_lib.lib().vmasr_dconv1d_fwd_slabs(int(Cin), int(Cout), int(groups), int(k), int(stride), int(pad), int(B), int(L)))
+
+
+def _dconv1d_ws(query, like, Cin, Cout, groups, k, stride, pad, B, L):
+    """(workspace or None, its bytes): 0 bytes for one slab, and for a refused shape, which the launcher then names."""
+    nbytes = query(Cin, Cout, groups, k, stride, pad, B, L)
+    return (_new(like, (nbytes // 4,)) if nbytes else None), nbytes
+
+
+def dconv1d_fwd(x, w, bias, stride, pad, act, groups=1):
+    """-> (y, pre) of the dense stride-1 convolution: y = GELU(pre), pre = conv + bias if act, else y = conv + bias and pre None."""
+    B, Cin, L = x.shape
+    Cout, _, k = w.shape
+    y = _new(x, (B, Cout, max(out_len(L, k, 1, pad), 0)))
+    pre = torch.empty_like(y) if act else None
+    ws, nbytes = _dconv1d_ws(_lib.lib().vmasr_dconv1d_fwd_workspace, x, Cin, Cout, groups, k, stride, pad, B, L)
+    _call(_lib.lib().vmasr_dconv1d_fwd, x, w, bias, y, pre, ws, nbytes, B, Cin, Cout, groups, L, k, stride, pad, int(bool(act)))
+    return y, pre
+
+
+def dconv1d_dgrad(gy, pre, w, x_shape, stride, pad, groups=1):
+    """-> dx of x_shape from gy (times GELU'(pre) if pre is given)."""
+    B, Cin, L = x_shape
+    Cout, _, k = w.shape
+    dx = _new(gy, tuple(x_shape))
+    ws, nbytes = _dconv1d_ws(_lib.lib().vmasr_dconv1d_dgrad_workspace, gy, Cin, Cout, groups, k, stride, pad, B, L)
+    _call(_lib.lib().vmasr_dconv1d_dgrad, gy, pre, w, dx, ws, nbytes, B, Cin, Cout, groups, L, k, stride, pad)
+    return dx
+
+
+def dconv1d_wgrad(x, gy, pre, w_shape, stride, pad, want_dw=True, want_db=True, groups=1):
+    """-> (dw of w_shape, db (Cout,)), each None unless wanted; sums in a fixed order (whole-K tiles or slab partials in a workspace)."""
+    B, Cin, L = x.shape
+    Cout, _, k = w_shape
+    if not (want_dw or want_db):
+        return None, None
+    ws, nbytes = _dconv1d_ws(_lib.lib().vmasr_dconv1d_wgrad_workspace, x, Cin, Cout, groups, k, stride, pad, B, L)
+    dw = _new(x, tuple(w_shape)) if want_dw else None
+    db = _new(x, (Cout,)) if want_db else None
+    _call(_lib.lib().vmasr_dconv1d_wgrad, x, gy, pre, dw, db, ws, nbytes, B, Cin, Cout, groups, L, k, stride, pad)
     return dw, db
 
 
