@@ -14,6 +14,7 @@
  *   vmasr_stft           wav2spectro                                            utils/stft.py:22-68
  *   vmasr_stft_bwd       autograd of torch.stft in the MR-STFT loss             model/loss.py:17-45
  *   vmasr_istft(_bwd)    spectro2wav (+ its autograd)                           utils/stft.py:71-115
+ *   vmasr_stft_db, vmasr_istft_scaled(_bwd)   the same under spectro_scale "dB" utils/stft.py:59-62, :95-97
  *
  * All functions are asynchronous on `stream` (a hipStream_t passed as void*; NULL = the
  * default stream), never synchronise the host, allocate nothing, and return 0 on
@@ -171,6 +172,23 @@ int vmasr_istft(const float *mag, const float *phase, float *wav, int32_t B, int
 int vmasr_istft_bwd(const float *mag, const float *phase, const float *g, float *dmag,
                     float *dphase, int32_t B, int32_t F, int32_t M, int32_t hop, int32_t win,
                     vmasr_stream_t stream);
+
+/* The reference's two spectrogram scales (utils/stft.py:59-66, :95-100).  LOG2: mag = log2(|S| + 1e-8), |S| = 2^mag.
+ * DB: mag = 10 log10 max(|S|^2, 1e-10) floored at (max over the call) - top_db, |S| = 10^(mag/20). */
+enum { VMASR_SCALE_LOG2 = 0, VMASR_SCALE_DB = 1 };
+/* vmasr_stft with the dB epilogue, in two launches: wav (B,T) -> mag = 10 log10 max(|S|^2, 1e-10), phase = angle(S), both
+ * (B, n_fft/2+1, 1+T/hop) fp32 (mag 16-byte aligned), then mag = max(mag, max(mag) - top_db) in place, ONE maximum over all B clips
+ * of the call (torchaudio's AmplitudeToDB on a 3-D input).  top_db < 0: no floor.  ws: scratch of vmasr_stft_db_workspace() bytes
+ * (one maximum per workgroup of the first launch; no atomics, no host read: capturable, the same bits every call). */
+size_t vmasr_stft_db_workspace(int32_t B, int32_t T, int32_t n_fft, int32_t hop);
+int vmasr_stft_db(const float *wav, float *mag, float *phase, int32_t B, int32_t T, int32_t n_fft, int32_t hop,
+                  int32_t win, int32_t normalized, float top_db, void *ws, size_t ws_bytes, vmasr_stream_t stream);
+/* vmasr_istft / vmasr_istft_bwd with the amplitude taken from `scale` (VMASR_SCALE_*); LOG2 runs the same kernels as those.
+ * ws: scratch of vmasr_istft_workspace() bytes. */
+int vmasr_istft_scaled(const float *mag, const float *phase, float *wav, int32_t B, int32_t F, int32_t M, int32_t hop,
+                       int32_t win, int32_t scale, void *ws, size_t ws_bytes, vmasr_stream_t stream);
+int vmasr_istft_scaled_bwd(const float *mag, const float *phase, const float *g, float *dmag, float *dphase, int32_t B,
+                           int32_t F, int32_t M, int32_t hop, int32_t win, int32_t scale, vmasr_stream_t stream);
 
 /* SNR, LSD, LSD-HF, LSD-LF of a batch (model/metric.py:5-67) in two launches (csrc/metrics.hip): out, tgt (B,T) fp32 and
  * hf (B) int64 on the device -> per_clip (B,4) fp32, columns snr, lsd, lsd_hf, lsd_lf.  STFT: center=True (reflect), periodic

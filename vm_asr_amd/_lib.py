@@ -202,6 +202,10 @@ SYMBOLS = {
     "vmasr_istft_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_istft": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "vmasr_istft_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "vmasr_stft_db_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "vmasr_stft_db": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_sz, c_vp]),
+    "vmasr_istft_scaled": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "vmasr_istft_scaled_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "vmasr_metrics_workspace": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vmasr_metrics": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "vmasr_gconv1d_supported": (ctypes.c_int, [c_i32] * 5),
