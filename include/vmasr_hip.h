@@ -700,6 +700,19 @@ int vmasr_stft_loss_fwd(const float *re_x, const float *im_x, const float *re_y,
                         vmasr_stream_t stream);
 int vmasr_stft_loss_bwd(const float *re_x, const float *im_x, const float *re_y, const float *im_y, int64_t n, const float *fin,
                         const float *g_sc, const float *g_ml, float *d_re, float *d_im, vmasr_stream_t stream);
+/* The same with the reference's EMPHASIZE_HIGH_FREQ weighting (model/loss.py:37-43: both magnitudes times linspace(1, 2, frames) along
+ * the FRAME axis of the (B, frames, bins) tensor, sic).  The spectra are (rows, frames) contiguous (rows = B x bins, as vmasr_stft writes
+ * them), n = rows x frames; frame m weighs w_m = w_first + (w_last - w_first) m / (frames - 1) (w_first when frames == 1):
+ *   sc = sqrt(S1w) / sqrt(S2w),  S1w = sum w_m^2 (mag_y - mag_x)^2,  S2w = sum w_m^2 mag_y^2;   ml as above (the weight cancels in the logs)
+ *   d mag_x = g_sc w_m^2 (mag_x - mag_y) / sqrt(S1w S2w) - g_ml sign(log mag_y - log mag_x) / (n mag_x)
+ * Same scratch (vmasr_stft_loss_blocks() x 3 fp64), same out[0..3] with S1w, S2w for S1, S2, same fixed summation order; no weight tensor
+ * is read or written.  All spectra and, for the backward, d_re / d_im 16-byte aligned; rows, frames > 0.  With frames == 1 and
+ * w_first == 1 the results are those of the unweighted pair, bit for bit. */
+int vmasr_stft_loss_w_fwd(const float *re_x, const float *im_x, const float *re_y, const float *im_y, int64_t rows, int64_t frames,
+                          float w_first, float w_last, double *partials, float *out, vmasr_stream_t stream);
+int vmasr_stft_loss_w_bwd(const float *re_x, const float *im_x, const float *re_y, const float *im_y, int64_t rows, int64_t frames,
+                          float w_first, float w_last, const float *fin, const float *g_sc, const float *g_ml, float *d_re, float *d_im,
+                          vmasr_stream_t stream);
 
 /* ---- strided grouped 1-D convolution of the multi-scale discriminator (vm_asr_amd/csrc/gconv1d.hip; model/discriminator.py:189-238) ----
  *   y[b, g Co + o, t] = bias[g Co + o] + sum_{c < Ci} sum_{j < k} w[g Co + o, c, j] x[b, g Ci + c, t stride + j - pad],   x = 0 outside [0, L)

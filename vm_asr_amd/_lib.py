@@ -90,6 +90,9 @@ SYMBOLS = {
     "vmasr_stft_loss_blocks": (c_i32, []),
     "vmasr_stft_loss_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vmasr_stft_loss_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vmasr_stft_loss_w_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_vp]),
+    "vmasr_stft_loss_w_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
+                                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vmasr_outproj_supported": (ctypes.c_int, [c_i32, c_i32]),
     "vmasr_outproj_fwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "vmasr_outproj_bwd": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),

@@ -5,7 +5,10 @@ Re-statement of model/loss.py: multi-resolution STFT loss (:17-184; resolutions 
 LSGAN / WGAN(-GP) / feature-matching losses (:188-260).  The STFTs (6 per step, 3 of them
 differentiated) run on the HIP front-end (`stft_reim`: vmasr_stft + vmasr_stft_bwd) instead of
 torch.stft — same arithmetic, and unlike rocFFT it can be captured in a HIP graph.  Only the
-reference's window ("hann_window") is supported.
+reference's window ("hann_window") is supported.  On the GPU the two terms of a resolution and
+their gradient are three launches of csrc/stftloss.hip (`_STFTLossFn`), with or without
+EMPHASIZE_HIGH_FREQ (the reference's linspace(1, 2) weight along the frame axis, folded into the
+same kernels); VMASR_STFT_LOSS=0 composes them from ATen ops instead, as the CPU path does.
 """
 import ctypes
 
@@ -39,29 +42,38 @@ def stft_magnitude(x, fft_size, hop_size, win_length, window, emphasize_high_fre
 class _STFTLossFn(torch.autograd.Function):
     """(sc, mag) of STFTLoss.forward from the (re, im) spectra of the generated signal x and the target y in ONE pass + a
     one-workgroup finish, gradient wrt x's spectrum in one pass (csrc/stftloss.hip) — instead of ~19 ATen launches forward and
-    ~35 backward per resolution."""
+    ~35 backward per resolution.  `emphasize`: the reference's EMPHASIZE_HIGH_FREQ weighting, linspace(1, 2, frames) along the
+    last axis of the (B, bins, frames) spectra, folded into the same passes (the *_w_* entry points; no weight tensor)."""
 
     @staticmethod
-    def forward(ctx, rx, ix, ry, iy):
+    def forward(ctx, rx, ix, ry, iy, emphasize=False):
         rx, ix, ry, iy = (t.float().contiguous() for t in (rx, ix, ry, iy))
         n, dev = rx.numel(), rx.device
         lib = _lib.lib()
         partials = torch.empty(int(lib.vmasr_stft_loss_blocks()) * 3, dtype=torch.float64, device=dev)
         out = torch.empty(4, dtype=torch.float32, device=dev)
-        _lib.call(lib.vmasr_stft_loss_fwd, rx, ix, ry, iy, n, partials, out)
+        if emphasize:
+            frames = rx.shape[-1]
+            _lib.call(lib.vmasr_stft_loss_w_fwd, rx, ix, ry, iy, n // frames, frames, 1.0, 2.0, partials, out)
+        else:
+            _lib.call(lib.vmasr_stft_loss_fwd, rx, ix, ry, iy, n, partials, out)
         ctx.save_for_backward(rx, ix, ry, iy, out)
+        ctx.emphasize = bool(emphasize)
         ctx.set_materialize_grads(False)
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, g_sc, g_ml):
         rx, ix, ry, iy, out = ctx.saved_tensors
-        dev = rx.device
         g_sc = None if g_sc is None else g_sc.float().reshape(1).contiguous()
         g_ml = None if g_ml is None else g_ml.float().reshape(1).contiguous()
         drx, dix = torch.empty_like(rx), torch.empty_like(ix)
-        _lib.call(_lib.lib().vmasr_stft_loss_bwd, rx, ix, ry, iy, rx.numel(), out, g_sc, g_ml, drx, dix)
-        return drx, dix, None, None
+        if ctx.emphasize:
+            frames = rx.shape[-1]
+            _lib.call(_lib.lib().vmasr_stft_loss_w_bwd, rx, ix, ry, iy, rx.numel() // frames, frames, 1.0, 2.0, out, g_sc, g_ml, drx, dix)
+        else:
+            _lib.call(_lib.lib().vmasr_stft_loss_bwd, rx, ix, ry, iy, rx.numel(), out, g_sc, g_ml, drx, dix)
+        return drx, dix, None, None, None
 
 
 class STFTLoss(torch.nn.Module):
@@ -76,12 +88,13 @@ class STFTLoss(torch.nn.Module):
     def forward(self, x, y):
         # (the reference moves its window buffer to x.device on every call — a host->device copy per
         # step; the HIP front-end builds the window in-kernel, so nothing is copied here)
-        if x.is_cuda and y.is_cuda and not self.emphasize_high_freq and knobs.get("VMASR_STFT_LOSS"):
-            # both magnitudes, the three sums of the two loss terms and their gradient as three launches (csrc/stftloss.hip)
+        if x.is_cuda and y.is_cuda and knobs.get("VMASR_STFT_LOSS"):
+            # both magnitudes, the three sums of the two loss terms and their gradient as three launches (csrc/stftloss.hip);
+            # emphasize_high_freq weighs the frames inside the same launches
             rx, ix = _stft.stft_reim(x.float(), self.fft_size, self.shift_size, self.win_length)
             with torch.no_grad():
                 ry, iy = _stft.stft_reim(y.float(), self.fft_size, self.shift_size, self.win_length)
-            return _STFTLossFn.apply(rx, ix, ry, iy)
+            return _STFTLossFn.apply(rx, ix, ry, iy, self.emphasize_high_freq)
         x_mag = stft_magnitude(x, self.fft_size, self.shift_size, self.win_length, None, self.emphasize_high_freq)
         y_mag = stft_magnitude(y, self.fft_size, self.shift_size, self.win_length, None, self.emphasize_high_freq)
         sc = torch.norm(y_mag - x_mag, p="fro") / torch.norm(y_mag, p="fro")
