@@ -625,7 +625,7 @@ def test_layer_norm_deferred_reduction_matches_immediate():
         L.defer_reduction = orig
         L.reset_uses()
     for a, b, c in zip(ref, got, got2):
-        assert torch.allclose(a, b, rtol=1e-5, atol=1e-5 * a.abs().max().item()) and torch.equal(b, c)
+        assert torch.equal(a, b) and torch.equal(b, c)      # (both reductions add the same partials in the same lane order)
 
 
 def test_layer_norm_deferred_queue_survives_an_aborted_backward():

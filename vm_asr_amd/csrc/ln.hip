@@ -376,14 +376,15 @@ VMASR_EXPORT int vmasr_layer_norm_bwd_reduce_multi(const float *const *parts, fl
                                                    const int32_t *nblks, const int32_t *Cs, int32_t n, vmasr_stream_t stream) {
     VMASR_REQUIRE(parts && dgammas && dbetas && nblks && Cs && n > 0, VMASR_EINVAL, "layer_norm_bwd_reduce_multi: null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // every item is checked before the first table is launched: a refused call has written nothing
+    for (int j = 0; j < n; ++j)
+        VMASR_REQUIRE(parts[j] && nblks[j] > 0 && Cs[j] > 0 && Cs[j] <= 1024, VMASR_EINVAL, "layer_norm_bwd_reduce_multi: bad item %d", j);
     for (int base = 0; base < n; base += kMaxReduceItems) {
         const int m = std::min(kMaxReduceItems, n - base);
         ReduceTable t{};
         int maxC = 0;
         double bytes = 0;
         for (int i = 0; i < m; ++i) {
-            VMASR_REQUIRE(parts[base + i] && nblks[base + i] > 0 && Cs[base + i] > 0 && Cs[base + i] <= 1024, VMASR_EINVAL,
-                          "layer_norm_bwd_reduce_multi: bad item %d", base + i);
             t.it[i] = ReduceItem{parts[base + i], dgammas[base + i], dbetas[base + i], nblks[base + i], Cs[base + i]};
             maxC = std::max(maxC, Cs[base + i]);
             bytes += (double)nblks[base + i] * 2 * Cs[base + i] * 4;

@@ -55,6 +55,13 @@ VMASR_EXPORT int vmasr_wgrad_finish_multi(const float *const *parts, float *cons
                                           const int32_t *Ns, const int32_t *Ks, const int32_t *lds, int32_t n, vmasr_stream_t stream) {
     VMASR_REQUIRE(parts && dws && dbs && Ss && Ns && Ks && lds && n > 0, VMASR_EINVAL, "wgrad_finish_multi: null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // every item is checked before the first table is launched: a refused call has written nothing
+    for (int j = 0; j < n; ++j) {
+        const float *e1 = e1s ? e1s[j] : nullptr, *e2 = e2s ? e2s[j] : nullptr;
+        VMASR_REQUIRE((!e1 || dbs[j]) && (!e2 || e1), VMASR_EINVAL, "wgrad_finish_multi: item %d: extra columns need the ones before them", j);
+        VMASR_REQUIRE(parts[j] && dws[j] && Ss[j] > 0 && Ns[j] > 0 && Ks[j] > 0 && lds[j] >= Ks[j] + (dbs[j] ? 1 : 0) + (e1 ? 1 : 0) + (e2 ? 1 : 0), VMASR_EINVAL,
+                      "wgrad_finish_multi: bad item %d", j);
+    }
     for (int base = 0; base < n; base += kMaxWgItems) {
         const int m = std::min(kMaxWgItems, n - base);
         WgTable t{};
@@ -63,9 +70,6 @@ VMASR_EXPORT int vmasr_wgrad_finish_multi(const float *const *parts, float *cons
         for (int i = 0; i < m; ++i) {
             const int j = base + i;
             float *e1 = e1s ? e1s[j] : nullptr, *e2 = e2s ? e2s[j] : nullptr;
-            VMASR_REQUIRE((!e1 || dbs[j]) && (!e2 || e1), VMASR_EINVAL, "wgrad_finish_multi: item %d: extra columns need the ones before them", j);
-            VMASR_REQUIRE(parts[j] && dws[j] && Ss[j] > 0 && Ns[j] > 0 && Ks[j] > 0 && lds[j] >= Ks[j] + (dbs[j] ? 1 : 0) + (e1 ? 1 : 0) + (e2 ? 1 : 0), VMASR_EINVAL,
-                          "wgrad_finish_multi: bad item %d", j);
             t.it[i] = WgItem{parts[j], dws[j], dbs[j], e1, e2, Ss[j], Ns[j], Ks[j], lds[j]};
             maxel = std::max(maxel, (long)Ns[j] * (Ks[j] + 3));
             bytes += (double)Ss[j] * Ns[j] * lds[j] * 4 + (double)Ns[j] * (Ks[j] + 1) * 4;
