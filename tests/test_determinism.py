@@ -71,6 +71,7 @@ def test_deterministic_mode_changes_no_value_beyond_rounding():
     switch on equal the default ones to fp32 rounding."""
     from vm_asr_amd import _lib
     from vm_asr_amd.dwconv import dwconv3x3_silu
+    from vm_asr_amd.ss2d_glue import ln_gate, ln_gate_pairs
     lib = _lib.lib()
     g = torch.Generator().manual_seed(0)
     x = torch.randn(2, 16, 64, 64, generator=g).cuda().requires_grad_(True)
@@ -83,15 +84,37 @@ def test_deterministic_mode_changes_no_value_beyond_rounding():
             t.grad = None
         dwconv3x3_silu(x, w, b).backward(gy)
         return [t.grad.clone() for t in (x, w, b)]
+
+    # ln_gate and ln_gate_pairs at shapes whose backward takes more than one pass per workgroup (65 chunks / 65 tiles over 64 workgroups)
+    def glue_inputs(B, H, W, D, pair):
+        ys = [3 * torch.randn(B, D, H * W, generator=g) + 0.5 for _ in range(2 if pair else 1)]
+        rest = [torch.randn(B, H, W, D, generator=g), 1 + 0.2 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)]
+        return [t.cuda().requires_grad_(True) for t in ys + rest], torch.randn(B, H, W, D, generator=g).cuda()
+    gate_in, gate_go = glue_inputs(1, 64, 257, 16, False)
+    pair_in, pair_go = glue_inputs(1, 80, 208, 8, True)
+
+    def run_glue(fn, ins, go):
+        for t in ins:
+            t.grad = None
+        fn(*ins, 1e-5).backward(go)
+        return [t.grad.clone() for t in ins]
     was = lib.vmasr_get_deterministic()
     try:
         lib.vmasr_set_deterministic(0)
         ref = run()
+        gref = run_glue(ln_gate, gate_in, gate_go) + run_glue(ln_gate_pairs, pair_in, pair_go)
         lib.vmasr_set_deterministic(1)
         d1, d2 = run(), run()
+        g1, g2 = (run_glue(ln_gate, gate_in, gate_go) + run_glue(ln_gate_pairs, pair_in, pair_go) for _ in range(2))
+        torch.cuda.synchronize()
+        assert lib.vmasr_det_timeouts() == 0
     finally:
         lib.vmasr_set_deterministic(was)
     for r, p, q in zip(ref, d1, d2):
+        assert torch.equal(p, q)
+        assert torch.allclose(r, p, rtol=1e-5, atol=1e-5 * r.abs().max().item())
+    assert len(gref) == 4 + 5
+    for r, p, q in zip(gref, g1, g2):
         assert torch.equal(p, q)
         assert torch.allclose(r, p, rtol=1e-5, atol=1e-5 * r.abs().max().item())
 
