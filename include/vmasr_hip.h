@@ -662,6 +662,24 @@ int vmasr_mlp_bwd(const void *x, const void *gy, const float *gamma, const float
                   void *xn_aug, void *gys, void *act_aug, void *gpre, float *mean, float *rstd, int64_t rows, int32_t d,
                   int32_t x_dtype, vmasr_stream_t stream);
 
+/* ---- the gated Mlp branch (MODEL.VSSM.GMLP) as one MFMA kernel (vm_asr_amd/csrc/gmlp.hip) ---------------------------
+ * `x + DropPath(gMlp(LayerNorm(x)))` (model/vmamba.py:512-538, :1815): [u ; z] = fc1(LN(x)) with fc1: d -> 2 hidden,
+ * y = x + scale * (fc2(u * GELU(z)) + b2), hidden = 4 d, d in {8,16,32,64} (vmasr_gmlp_supported).  Arguments, dtypes and
+ * alignment as for vmasr_mlp_fwd / vmasr_mlp_bwd, with
+ *   w1 (8d, d) bf16 = fc1.weight (rows 0 .. 4d-1 = u, 4d .. 8d-1 = z), b1 (8d) fp32;  w2 (d, 4d) bf16, b2 (d) fp32;
+ *   w1t (d, 8d) = fc1.weight^T, w2t (4d, d) = fc2.weight^T;
+ *   gpre (rows, 8d) bf16 = [du | dz], the gradient wrt fc1's output:    gpre^T . xn_aug = [dW1 | db1 | 0]
+ *   act_aug (rows, 4d + 8) bf16 = [u * GELU(z) | 1 0 ...]:               gys^T . act_aug = [dW2 | db2 | 0]
+ * A width outside the set or rows <= 0 returns VMASR_EINVAL before any launch. */
+int vmasr_gmlp_supported(int32_t d, int32_t hidden);
+int vmasr_gmlp_fwd(const void *x, const float *gamma, const float *beta, float eps, const void *w1, const float *b1,
+                   const void *w2, const float *b2, const float *scale, int32_t rows_per_sample, void *y, int64_t rows,
+                   int32_t d, int32_t x_dtype, vmasr_stream_t stream);
+int vmasr_gmlp_bwd(const void *x, const void *gy, const float *gamma, const float *beta, float eps, const void *w1,
+                   const void *w1t, const float *b1, const void *w2t, const float *scale, int32_t rows_per_sample, void *dxn,
+                   void *xn_aug, void *gys, void *act_aug, void *gpre, float *mean, float *rstd, int64_t rows, int32_t d,
+                   int32_t x_dtype, vmasr_stream_t stream);
+
 /* ---- the input side of SS2D.forwardv2 as one MFMA kernel (vm_asr_amd/csrc/mlp.hip: inproj_kernel) ----------------------
  * xz = in_proj(LayerNorm(x)) (model/vmamba.py:1826-1827, 1535); x', z = xz.chunk(2, -1); xT = x'.permute(0,3,1,2);
  * sz = SiLU(z) (:1537-1542) — LayerNorm + Linear + vmasr_ss2d_pre_fwd in one launch, under bf16 autocast, for x (rows, d) fp32 or
@@ -872,6 +890,8 @@ enum {
     VMASR_K_WEIGHT_T,           /* (n, Cout, k, Cin) fp32 weight operand -> the input gradient's (n, Cin, k*Cout) operand, bf16 pair or fp32 */
     VMASR_K_MLP_FWD,            /* LayerNorm + fc1 + GELU + fc2 + residual of a VSS block as one MFMA kernel */
     VMASR_K_MLP_BWD,
+    VMASR_K_GMLP_FWD,           /* the gated form: LayerNorm + fc1 + u * GELU(z) + fc2 + residual as one MFMA kernel (csrc/gmlp.hip) */
+    VMASR_K_GMLP_BWD,
     VMASR_K_INPROJ_FWD,         /* LayerNorm + in_proj + chunk + SiLU(z) + channel-first copy of a VSS block's SS2D as one MFMA kernel */
     VMASR_K_INPROJ_BWD,
     VMASR_K_SS2D_DEEP_XPROJ,    /* deep-stage SS2D core: x_proj (x -> x_dbl)                                    */

@@ -1,6 +1,7 @@
 """Fused Mlp branch (csrc/mlp.hip) vs the unfused module path (LayerNorm -> Linear -> GELU -> Linear -> add, hipBLASLt + ATen +
 ln.hip) at the generator's shapes (B = $B, default 4), bf16 autocast: device time per call, forward and forward+backward,
-REP calls captured in a HIP graph and replayed (dev tool)."""
+REP calls captured in a HIP graph and replayed (dev tool).
+--gated: the gated Mlp (MODEL.VSSM.GMLP; csrc/gmlp.hip, vm_asr_amd/gmlp.py) against its module path instead."""
 import os
 import sys
 
@@ -9,8 +10,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vm_asr_amd.layernorm import LayerNorm  # noqa: E402
+from vm_asr_amd.gmlp import fused_gmlp_residual  # noqa: E402
 from vm_asr_amd.mlp import fused_mlp_residual  # noqa: E402
-from vm_asr_amd.vmamba import Mlp  # noqa: E402
+from vm_asr_amd.vmamba import Mlp, gMlp  # noqa: E402
+
+GATED = "--gated" in sys.argv[1:]
 
 B, REP = int(os.environ.get("B", "4")), int(os.environ.get("REP", "50"))
 SHAPES = [(8, 256, torch.float32), (16, 128, torch.float32), (16, 128, torch.bfloat16), (32, 64, torch.bfloat16), (64, 32, torch.bfloat16),
@@ -47,14 +51,15 @@ for d, H, xdt in SHAPES:
     if ONLY and (int(ONLY) != d or xdt != (torch.float32 if d == 8 else torch.bfloat16)):
         continue
     torch.manual_seed(0)
-    norm, mlp = LayerNorm(d).cuda(), Mlp(d, 4 * d).cuda()
+    norm, mlp = LayerNorm(d).cuda(), (gMlp if GATED else Mlp)(d, 4 * d).cuda()
     norm.feeds_gemm = True
     x = torch.randn(B, H, H, d, device="cuda").to(xdt)
     gy = torch.randn(B, H, H, d, device="cuda").to(xdt)
     res = {}
     from vm_asr_amd import _lib
-    offered = bool(_lib.lib().vmasr_mlp_supported(d, 4 * d))
-    for name, f in (("fused", lambda xi: fused_mlp_residual(xi, norm, mlp)), ("unfused", lambda xi: xi + mlp(norm(xi)))):
+    offered = bool((_lib.lib().vmasr_gmlp_supported if GATED else _lib.lib().vmasr_mlp_supported)(d, 4 * d))
+    fused = fused_gmlp_residual if GATED else fused_mlp_residual
+    for name, f in (("fused", lambda xi: fused(xi, norm, mlp)), ("unfused", lambda xi: xi + mlp(norm(xi)))):
         if (MODE and MODE != name) or (name == "fused" and not offered):      # d = 128: built, not offered
             res[name] = (0.0, 0.0)
             continue
@@ -69,5 +74,5 @@ for d, H, xdt in SHAPES:
             y.backward(gy)
         res[name] = (timed(fwd), timed(fwdbwd))
     rows = B * H * H
-    print(f"d={d:4d} rows={rows:7d} x {str(xdt)[6:]:8s}: fused fwd {res['fused'][0]:7.1f} us  fwd+bwd {res['fused'][1]:7.1f} us | unfused fwd "
+    print(f"{'gMlp' if GATED else 'Mlp'} d={d:4d} rows={rows:7d} x {str(xdt)[6:]:8s}: fused fwd {res['fused'][0]:7.1f} us  fwd+bwd {res['fused'][1]:7.1f} us | unfused fwd "
           f"{res['unfused'][0]:7.1f} us  fwd+bwd {res['unfused'][1]:7.1f} us   (x in + y out: {rows * d * 2 * x.element_size() / 1e6:.1f} MB)")

@@ -36,7 +36,7 @@ const char *kNames[VMASR_K_COUNT] = {
     "layer_norm_bwd_reduce", "small_linear_fwd", "small_linear_bwd", "small_linear_reduce",
     "xproj_fwd", "xproj_bwd_a", "xproj_bwd_b", "spectral_power_iter", "im2col_kx1", "col2im_kx1", "split_bf16", "bias_gelu",
     "ss2d_transpose", "ss2d_fwd_agg", "ss2d_carry", "ss2d_fwd_apply", "ss2d_merge", "ss2d_bwd_agg", "ss2d_bwd_apply",
-    "ss2d_pre", "ln_gate", "stack_rows", "feat_l1", "adamw", "conv_post", "conv_post_bwd_gelu", "weight_transpose", "mlp_fwd", "mlp_bwd", "inproj_fwd", "inproj_bwd",
+    "ss2d_pre", "ln_gate", "stack_rows", "feat_l1", "adamw", "conv_post", "conv_post_bwd_gelu", "weight_transpose", "mlp_fwd", "mlp_bwd", "gmlp_fwd", "gmlp_bwd", "inproj_fwd", "inproj_bwd",
     "ss2d_deep_xproj", "ss2d_deep_fwd", "ss2d_deep_bwd", "ss2d_deep_xbwd", "outproj_fwd", "outproj_bwd", "stft_loss",
     "conv_mfma_fwd", "conv_mfma_dgrad", "conv_mfma_wgrad", "wgrad_finish", "skinny_linear", "metrics", "resample_design", "degrade_batch",
     "gconv1d_fwd", "gconv1d_dgrad", "gconv1d_wgrad", "gconv1d_wgrad_reduce",

@@ -4,7 +4,7 @@
 outside the declared set raises ValueError at the read.  Nothing else under vm_asr_amd/ reads a VMASR_* variable.  Readers:
 "python" = this package through get(), for the switches that existed when this registry was written: tests/test_knobs.py pins exactly
 that set and its defaults in a fixed table.  A python-read switch added later cannot join the table, so it carries "python:<feature>"
-(so far "python:msd") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py, tests/test_msd_tail.py);
+(so far "python:msd", "python:gmlp") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py, tests/test_msd_tail.py, tests/test_gmlp.py);
 "csrc" = a static `getenv` in vm_asr_amd/csrc (read once per process; listed here with the
 default the C++ code applies); "external" = bench.py, the tests, tools/ or oracle/, which read their own names directly.
 No torch import: tests/test_knobs.py and tools load this module without a GPU stack.
@@ -104,6 +104,8 @@ KNOBS = {k.name: k for k in (
     _k("VMASR_XPROJ_MAX_D", "int", 512, "largest d_inner that takes the x_proj row kernels instead of einsums; read at import"),
     # ---- generator operators (1: the HIP operator, 0: the unfused chain)
     _k("VMASR_FUSED_MLP", "flag", 1, "LayerNorm + Mlp + residual of a VSS block as one operator (mlp.py)"),
+    _k("VMASR_FUSED_GMLP", "flag", 1, "LayerNorm + gated Mlp (MODEL.VSSM.GMLP) + residual of a VSS block as one operator (gmlp.py)",
+       reader="python:gmlp"),
     _k("VMASR_FUSED_INPROJ", "flag", 1, "LayerNorm + in_proj + split + SiLU as one operator (inproj.py)"),
     _k("VMASR_FUSED_OUTPROJ", "flag", 1, "out_proj + DropPath + residual as one operator (outproj.py)"),
     _k("VMASR_SS2D_FUSED", "flag", 1, "the d_state-1 SS2D core (x_proj, dt_proj, four-direction scan, merge) as one operator (ss2d_core.py)"),

@@ -41,8 +41,11 @@ def supported(x, norm, mlp):
 
 
 class _FusedMlpFn(torch.autograd.Function):
+    """entry: "vmasr_mlp", or "vmasr_gmlp" for the gated form (gmlp.py: fc1 has 2 * hidden rows, the kernels' argument lists are
+    the same) — the shapes below are read off the weights, so one function serves both."""
+
     @staticmethod
-    def forward(ctx, x, gamma, beta, w1, b1, w2, b2, scale, eps):
+    def forward(ctx, x, gamma, beta, w1, b1, w2, b2, scale, eps, entry="vmasr_mlp"):
         d = x.shape[-1]
         x2 = _lib.rows2d(x, d)
         rows = x2.shape[0]
@@ -52,10 +55,11 @@ class _FusedMlpFn(torch.autograd.Function):
         rps = rows // scale.numel() if scale is not None else 0
         sc = None if scale is None else scale.detach().float().contiguous().view(-1)
         y = torch.empty_like(x2)
-        _lib.call(_lib.lib().vmasr_mlp_fwd, x2, g32, be32, float(eps), w1b, b1f, w2b, b2f, sc, rps, y, rows, d, _lib.torch_dtype_code(x2.dtype))
+        _lib.call(getattr(_lib.lib(), entry + "_fwd"), x2, g32, be32, float(eps), w1b, b1f, w2b, b2f, sc, rps, y, rows, d, _lib.torch_dtype_code(x2.dtype))
         ctx.save_for_backward(x2, g32, be32, w1b, b1f, w2b, sc)
         ctx.wts = (bf16_shadow_t(w1, w1b), bf16_shadow_t(w2, w2b))
         ctx.meta = (x.shape, eps, rps, gamma.dtype, beta.dtype, w1.dtype, b1.dtype, w2.dtype, b2.dtype)
+        ctx.entry = entry
         if any(ctx.needs_input_grad[1:3]):
             _ln.note_use(gamma, beta)
         ctx.fresh = lambda: gamma.grad is None and beta.grad is None and _ln.used_once(gamma, beta)
@@ -70,7 +74,7 @@ class _FusedMlpFn(torch.autograd.Function):
         x2, g32, be32, w1b, b1f, w2b, sc = ctx.saved_tensors
         shape, eps, rps, gdt, bedt, w1dt, b1dt, w2dt, b2dt = ctx.meta
         rows, d = x2.shape
-        hd = w1b.shape[0]
+        hd, h1 = w2b.shape[1], w1b.shape[0]             # hidden; fc1's rows (hidden, gated: 2 * hidden)
         gy2 = gy.reshape(rows, d).to(x2.dtype)
         if not gy2.is_contiguous():
             gy2 = gy2.contiguous()
@@ -83,9 +87,9 @@ class _FusedMlpFn(torch.autograd.Function):
         xn_aug = torch.empty((rows, d + 8), **bf)
         gys = torch.empty((rows, d), **bf)
         act_aug = torch.empty((rows, hd + 8), **bf)
-        gpre = torch.empty((rows, hd), **bf)
+        gpre = torch.empty((rows, h1), **bf)
         stats = torch.empty((2, rows), dtype=torch.float32, device=dev)
-        _lib.call(lib.vmasr_mlp_bwd, x2, gy2, g32, be32, float(eps), w1b, w1t, b1f, w2t, sc, rps, dxn, xn_aug, gys, act_aug, gpre,
+        _lib.call(getattr(lib, ctx.entry + "_bwd"), x2, gy2, g32, be32, float(eps), w1b, w1t, b1f, w2t, sc, rps, dxn, xn_aug, gys, act_aug, gpre,
                   stats[0], stats[1], rows, d, _lib.torch_dtype_code(x2.dtype))
         # dx = gy + LayerNorm'(dxn); dgamma, dbeta  (one launch: csrc/ln.hip with the residual gradient folded in)
         dx = torch.empty_like(x2)
@@ -100,7 +104,7 @@ class _FusedMlpFn(torch.autograd.Function):
         fresh_w = _ln.fresh(*ctx.wparams)
         dw1, db1 = weight_grad_finished(gpre, xn_aug, d, ctx.wparams[0], ctx.wparams[1], fresh_w)
         dw2, db2 = weight_grad_finished(gys, act_aug, hd, ctx.wparams[2], ctx.wparams[3], fresh_w)
-        return (dx.view(shape), dg_.to(gdt), db_.to(bedt), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None)
+        return (dx.view(shape), dg_.to(gdt), db_.to(bedt), dw1.to(w1dt), db1.to(b1dt), dw2.to(w2dt), db2.to(b2dt), None, None, None)
 
 
 def fused_mlp_residual(x, norm, mlp, scale=None):

@@ -35,6 +35,7 @@ from . import ss2d_core as _ss2d
 from . import ss2d_deep as _deep
 from . import ss2d_glue as _glue
 from . import xproj as _xproj
+from . import gmlp as _gmlp
 from . import mlp as _mlp
 from . import inproj as _inproj
 from . import outproj as _outproj
@@ -159,6 +160,26 @@ class Mlp(nn.Module):
 
     def forward(self, x):
         return self.drop(self.fc2(self.drop(self.act(self.fc1(x)))))
+
+
+class gMlp(nn.Module):
+    """model/vmamba.py:512-538: fc1 makes both halves, u, z = fc1(x).chunk(2); fc2(u * act(z)); one dropout, after fc2."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.0,
+                 channels_first=False):
+        super().__init__()
+        self.channel_first = channels_first
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        Linear = Linear2d if channels_first else _Linear
+        self.fc1 = Linear(in_features, 2 * hidden_features)
+        self.act = act_layer()
+        self.fc2 = Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+
+    def forward(self, x):
+        x, z = self.fc1(x).chunk(2, dim=(1 if self.channel_first else -1))
+        return self.drop(self.fc2(x * self.act(z)))
 
 
 def _strip(tag: str, value: str):
@@ -465,10 +486,8 @@ class VSSBlock(nn.Module):
         if self.ssm_branch and isinstance(self.norm, LayerNorm) and not post_norm and not channel_first:
             self.norm.feeds_gemm = True   # -> SS2D.in_proj
         if self.mlp_branch:
-            if gmlp:
-                raise NotImplementedError("gMlp is not reachable from any shipped config (config.py:112)")
             self.norm2 = norm_layer(hidden_dim)
-            self.mlp = Mlp(in_features=hidden_dim, hidden_features=int(hidden_dim * mlp_ratio),
+            self.mlp = (gMlp if gmlp else Mlp)(in_features=hidden_dim, hidden_features=int(hidden_dim * mlp_ratio),
                            act_layer=mlp_act_layer, drop=mlp_drop_rate, channels_first=channel_first)
             if isinstance(self.norm2, LayerNorm) and not post_norm and not channel_first:
                 self.norm2.feeds_gemm = True  # -> Mlp.fc1
@@ -486,6 +505,9 @@ class VSSBlock(nn.Module):
             elif _mlp.supported(x, self.norm2, self.mlp):
                 # LayerNorm + fc1 + GELU + fc2 + residual (+ the stochastic-depth scale) as ONE MFMA kernel (csrc/mlp.hip)
                 x = _mlp.fused_mlp_residual(x, self.norm2, self.mlp, self.drop_path._mask(x) if self.drop_path.active() else None)
+            elif isinstance(self.mlp, gMlp) and _gmlp.supported(x, self.norm2, self.mlp):
+                # the gated form (MODEL.VSSM.GMLP): LayerNorm + fc1 + u * GELU(z) + fc2 + residual as ONE MFMA kernel (csrc/gmlp.hip)
+                x = _gmlp.fused_gmlp_residual(x, self.norm2, self.mlp, self.drop_path._mask(x) if self.drop_path.active() else None)
             else:
                 x = self.drop_path.residual(x, self.mlp(self.norm2(x)))
         return x
