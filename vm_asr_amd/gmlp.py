@@ -9,33 +9,15 @@ writes dxn plus the bf16 operands of the weight-gradient GEMMs (gpre = [du | dz]
 the two GEMMs — the autograd function is mlp.py's, with the gated entry points: same bf16 shadows and transposed shadows, same
 deferred LayerNorm / weight-gradient reductions.  No CPU fallback.
 """
-import torch
-
 from . import _lib, knobs
-from .mlp import _FusedMlpFn
+from .mlp import _FusedMlpFn, mlp_hidden
 
 __all__ = ["fused_gmlp_residual", "supported"]
 
 
 def supported(x, norm, mlp):
-    """GPU, bf16 autocast, fp32 or bf16 channel-last stream, a gMlp (fc1: d -> 2 * hidden, exact GELU, no active dropout) of a
-    supported width.  (The channel-first form — Linear2d / LayerNorm2d, chunk on axis 1 — is never the row kernel.)"""
-    if not knobs.get("VMASR_FUSED_GMLP") or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    if not _lib.bf16_autocast():
-        return False
-    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
-    if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear) and isinstance(norm, torch.nn.LayerNorm)
-            and all(type(m).__name__ not in ("Linear2d", "LayerNorm2d") for m in (fc1, fc2, norm))):
-        return False
-    if getattr(mlp, "channel_first", False) or not isinstance(mlp.act, torch.nn.GELU) or getattr(mlp.act, "approximate", "none") != "none":
-        return False
-    if (mlp.drop.p != 0.0 and mlp.training) or fc1.bias is None or fc2.bias is None or norm.weight is None or norm.bias is None:
-        return False
-    d = x.shape[-1]
-    if tuple(norm.normalized_shape) != (d,) or fc1.in_features != d or fc2.out_features != d or fc1.out_features != 2 * fc2.in_features:
-        return False
-    return bool(_lib.lib().vmasr_gmlp_supported(int(d), int(fc2.in_features)))
+    hidden = knobs.get("VMASR_FUSED_GMLP") and mlp_hidden(x, norm, mlp, True)
+    return bool(hidden and _lib.lib().vmasr_gmlp_supported(int(x.shape[-1]), int(hidden)))
 
 
 def fused_gmlp_residual(x, norm, mlp, scale=None):

@@ -14,24 +14,16 @@ from . import _lib, knobs
 from . import layernorm as _ln
 from .wgrad import weight_grad_finished
 from .linear import bf16_shadow, bf16_shadow_t
+from .mlp import amp_stream, row_layernorm, row_linear
 
 __all__ = ["fused_in_proj", "supported"]
 
 
 def supported(x, norm, in_proj):
-    if not knobs.get("VMASR_FUSED_INPROJ") or not x.is_cuda or x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    if not _lib.bf16_autocast():
-        return False
-    if not isinstance(in_proj, torch.nn.Linear) or type(in_proj).__name__ == "Linear2d" or in_proj.bias is not None:
+    if not knobs.get("VMASR_FUSED_INPROJ") or x.dim() != 4 or not amp_stream(x) or not row_linear(in_proj, False):
         return False
     d = x.shape[-1]
-    if isinstance(norm, torch.nn.LayerNorm) and type(norm).__name__ != "LayerNorm2d":
-        if tuple(norm.normalized_shape) != (d,) or norm.weight is None or norm.bias is None:
-            return False
-    elif not isinstance(norm, torch.nn.Identity):
-        return False
-    if in_proj.in_features != d:
+    if not (row_layernorm(norm, d) or isinstance(norm, torch.nn.Identity)) or in_proj.in_features != d:
         return False
     return bool(_lib.lib().vmasr_inproj_supported(int(d), int(in_proj.out_features), int(x.shape[1] * x.shape[2])))
 

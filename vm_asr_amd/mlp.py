@@ -19,25 +19,38 @@ from .linear import bf16_shadow, bf16_shadow_t
 __all__ = ["fused_mlp_residual", "supported"]
 
 
+def amp_stream(*streams):
+    """GPU tensors in fp32 / bf16 under bf16 autocast (this and the two below: shared with gmlp.py, inproj.py, outproj.py)."""
+    return all(t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) for t in streams) and _lib.bf16_autocast()
+
+
+def row_linear(m, bias):
+    """An nn.Linear over the last axis with / without a bias.  (Linear2d / LayerNorm2d act on axis 1: never a row kernel.)"""
+    return isinstance(m, torch.nn.Linear) and type(m).__name__ != "Linear2d" and (m.bias is not None) == bias
+
+
+def row_layernorm(m, d):
+    """An affine nn.LayerNorm of width d over the last axis."""
+    return (isinstance(m, torch.nn.LayerNorm) and type(m).__name__ != "LayerNorm2d" and tuple(m.normalized_shape) == (d,)
+            and m.weight is not None and m.bias is not None)
+
+
+def mlp_hidden(x, norm, mlp, gated):
+    """-> the hidden width if x + mlp(norm(x)) is what the fused Mlp (gated: gMlp, fc1: d -> 2 * hidden) computes, else 0: channel-last
+    stream, biased row Linears, exact GELU, no active dropout.  Knob and width rule are the callers'."""
+    d, fc1, fc2 = x.shape[-1], getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
+    if not (amp_stream(x) and row_linear(fc1, True) and row_linear(fc2, True) and row_layernorm(norm, d)):
+        return 0
+    if getattr(mlp, "channel_first", False) or not isinstance(mlp.act, torch.nn.GELU) or getattr(mlp.act, "approximate", "none") != "none":
+        return 0
+    if (mlp.drop.p != 0.0 and mlp.training) or fc1.in_features != d or fc2.out_features != d:
+        return 0
+    return fc2.in_features if fc1.out_features == (2 if gated else 1) * fc2.in_features else 0
+
+
 def supported(x, norm, mlp):
-    """GPU, bf16 autocast, fp32 channel-last stream, plain Mlp (GELU exact, no dropout) of a supported width.
-    (The channel-first subclasses Linear2d / LayerNorm2d act on axis 1: never the row kernel, whatever x.shape[-1] is.)"""
-    if not knobs.get("VMASR_FUSED_MLP") or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    if not _lib.bf16_autocast():
-        return False
-    fc1, fc2 = getattr(mlp, "fc1", None), getattr(mlp, "fc2", None)
-    if not (isinstance(fc1, torch.nn.Linear) and isinstance(fc2, torch.nn.Linear) and isinstance(norm, torch.nn.LayerNorm)
-            and all(type(m).__name__ not in ("Linear2d", "LayerNorm2d") for m in (fc1, fc2, norm))):
-        return False
-    if not isinstance(mlp.act, torch.nn.GELU) or getattr(mlp.act, "approximate", "none") != "none":
-        return False
-    if (mlp.drop.p != 0.0 and mlp.training) or fc1.bias is None or fc2.bias is None or norm.weight is None or norm.bias is None:
-        return False
-    d = x.shape[-1]
-    if tuple(norm.normalized_shape) != (d,) or fc1.in_features != d or fc2.out_features != d or fc2.in_features != fc1.out_features:
-        return False
-    return bool(_lib.lib().vmasr_mlp_supported(int(d), int(fc1.out_features)))
+    hidden = knobs.get("VMASR_FUSED_MLP") and mlp_hidden(x, norm, mlp, False)
+    return bool(hidden and _lib.lib().vmasr_mlp_supported(int(x.shape[-1]), int(hidden)))
 
 
 class _FusedMlpFn(torch.autograd.Function):

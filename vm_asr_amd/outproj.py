@@ -14,19 +14,14 @@ from . import _lib, knobs
 from .wgrad import weight_grad_finished
 from . import layernorm as _ln
 from .linear import bf16_shadow, bf16_shadow_t
+from .mlp import amp_stream, row_linear
 
 __all__ = ["fused_out_proj_residual", "supported"]
 
 
 def supported(g, out_proj, x, dropout=None):
     """GPU, bf16 autocast, bf16 gate output, fp32 / bf16 stream, bias-free out_proj of a supported width, no active dropout."""
-    if not knobs.get("VMASR_FUSED_OUTPROJ") or not (g.is_cuda and x.is_cuda):
-        return False
-    if not _lib.bf16_autocast():
-        return False
-    if g.dtype != torch.bfloat16 or x.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    if not isinstance(out_proj, torch.nn.Linear) or type(out_proj).__name__ == "Linear2d" or out_proj.bias is not None:
+    if not knobs.get("VMASR_FUSED_OUTPROJ") or not amp_stream(g, x) or g.dtype != torch.bfloat16 or not row_linear(out_proj, False):
         return False
     if dropout is not None and not isinstance(dropout, torch.nn.Identity) and getattr(dropout, "p", 0.0) != 0.0 and dropout.training:
         return False

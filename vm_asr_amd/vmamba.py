@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
-from . import knobs
+from . import _lib, knobs
 from .csm import CrossMergeHIP, CrossScanF32, CrossScanHIP
 from . import ss2d_core as _ss2d
 from . import ss2d_deep as _deep
@@ -195,6 +195,26 @@ def _strip(tag: str, value: str):
 _XPROJ_MAX_D = knobs.get("VMASR_XPROJ_MAX_D")
 
 
+def product_ops_in_force(on_gpu, force_fp32=False, no_einsum=False, SelectiveScan=None, CrossScan=None, CrossMerge=None, **_):
+    """A GPU tensor, fp32 scan streams, x_proj as an einsum and none of forward_corev2's operator hooks replaced: only then may a
+    fused operator stand in.  forward_corev2 asks with its own arguments, SS2D.forward with those `forward_core` was bound with."""
+    return bool(on_gpu and force_fp32 and not no_einsum and SelectiveScan is SelectiveScanCore and CrossScan is CrossScanHIP and CrossMerge is CrossMergeHIP)
+
+
+def core_path(d_state, dt_rank, d_inner, H, W, dtype, product_ops, delta_softplus=True, k_group=4, pairs_wanted=False):
+    """Which operator computes cross-scan .. cross-merge of one SS2D call (no tensor is touched), in priority order: "pairs" / "fused":
+    csrc/ss2d.hip (d_state 1, dt_rank 1, d_inner <= 32), its pair outputs left un-merged for a caller that gates them itself
+    (ln_gate_pairs) or merged; "deep": csrc/ss2d_deep.hip (d_inner 64..512, H*W <= 4096); "xproj": csrc/xproj.hip / xproj_n.hip
+    write scan-ready fp32 streams for the scan operator; "chain": CrossScan, einsum / conv1d, SelectiveScan, CrossMerge as plugged
+    in.  The fused cores are softplus, four-direction operators."""
+    if product_ops and delta_softplus and k_group == 4:
+        if _ss2d.supported(d_state, dt_rank, d_inner, H, W):
+            return "pairs" if pairs_wanted and _glue.pairs_supported(d_inner, H, W, dtype) else "fused"
+        if _deep.supported(d_state, dt_rank, d_inner, H, W, dtype):
+            return "deep"
+    return "xproj" if product_ops and _xproj.supported(d_state, dt_rank, d_inner) and d_inner <= _XPROJ_MAX_D else "chain"
+
+
 class SS2D(nn.Module):
     def __init__(self, d_model=96, d_state=16, ssm_ratio=2.0, dt_rank="auto", act_layer=nn.SiLU,
                  d_conv=3, conv_bias=True, dropout=0.0, bias=False, dt_min=0.001, dt_max=0.1,
@@ -314,61 +334,51 @@ class SS2D(nn.Module):
         LayerNorm-gate operator of forward())."""
         x_proj_weight, dt_projs_weight, dt_projs_bias = self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias
         A_logs, Ds = self.A_logs, self.Ds
-        out_norm = getattr(self, "out_norm", None)
         B, D, H, W = x.shape
         D, N = A_logs.shape
         K, D, R = dt_projs_weight.shape
         L = H * W
 
-        hip_default = (x.is_cuda and force_fp32 and not no_einsum and CrossScan is CrossScanHIP
-                       and SelectiveScan is SelectiveScanCore and CrossMerge is CrossMergeHIP)
-        if hip_default and delta_softplus and K == 4 and _ss2d.supported(N, R, D, H, W):
-            # the whole core (cross-scan, x_proj, dt_proj, 4 scans, cross-merge) as one fused operator: the
-            # high-resolution stages (d_state 1, dt_rank 1, d_inner <= 32) — csrc/ss2d.hip
+        path = core_path(N, R, D, H, W, x.dtype, product_ops_in_force(x.is_cuda, force_fp32, no_einsum, SelectiveScan, CrossScan, CrossMerge),
+                         delta_softplus, K)
+        if path == "fused":     # cross-scan, x_proj, dt_proj, 4 scans, cross-merge as one operator
             y = _ss2d.ss2d_core(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)
-            return y if merged_only else self._merge_norm(y, x, B, H, W, to_dtype)
-        if hip_default and delta_softplus and K == 4 and _deep.supported(N, R, D, H, W, x.dtype):
-            # the deep stages (dt_rank 2..8, d_inner 64..512, H*W <= 4096): whole rows per workgroup, cross-scan / cross-merge
-            # through an LDS image, x_proj as a small kernel in front — csrc/ss2d_deep.hip
+        elif path == "deep":
             y = _deep.ss2d_deep(x, x_proj_weight, dt_projs_weight, dt_projs_bias, A_logs, Ds)
-            return y if merged_only else self._merge_norm(y, x, B, H, W, to_dtype)
-        if (hip_default and _xproj.supported(N, R, D) and D <= _XPROJ_MAX_D):
-            # (position-parallel kernels for d_inner <= 32, row-parallel ones above; see _XPROJ_MAX_D)
-            # HIP fast path: the scan streams are produced in fp32 directly and x_proj/dt_proj are one
-            # memory-bound kernel writing scan-ready fp32 tensors (no einsum / contiguous / cast passes)
+        elif path == "xproj":
+            # fp32 scan streams directly; x_proj/dt_proj as one memory-bound kernel writing scan-ready tensors (no einsum / cast passes)
             xs = CrossScanF32.apply(x)                                         # (B, K, D, L) fp32
             dts, Bs, Cs = _xproj.x_proj_dt(xs, x_proj_weight, dt_projs_weight, N)
             ys = SelectiveScan.apply(xs.view(B, -1, L), dts, -torch.exp(A_logs.to(torch.float)), Bs, Cs,
                                      Ds.to(torch.float), dt_projs_bias.view(-1).to(torch.float), delta_softplus,
                                      nrows, backnrows, ssoflex).view(B, K, -1, H, W)
             y = CrossMerge.apply(ys)
-            return y if merged_only else self._merge_norm(y, x, B, H, W, to_dtype)
-
-        xs = CrossScan.apply(x)  # (B, K, D, L)
-        if no_einsum:
-            x_dbl = F.conv1d(xs.view(B, -1, L), x_proj_weight.view(-1, D, 1), groups=K)
-            dts, Bs, Cs = torch.split(x_dbl.view(B, K, -1, L), [R, N, N], dim=2)
-            dts = F.conv1d(dts.contiguous().view(B, -1, L), dt_projs_weight.view(K * D, -1, 1), groups=K)
         else:
-            x_dbl = torch.einsum("b k d l, k c d -> b k c l", xs, x_proj_weight)
-            dts, Bs, Cs = torch.split(x_dbl, [R, N, N], dim=2)
-            dts = torch.einsum("b k r l, k d r -> b k d l", dts, dt_projs_weight)
+            xs = CrossScan.apply(x)  # (B, K, D, L)
+            if no_einsum:
+                x_dbl = F.conv1d(xs.view(B, -1, L), x_proj_weight.view(-1, D, 1), groups=K)
+                dts, Bs, Cs = torch.split(x_dbl.view(B, K, -1, L), [R, N, N], dim=2)
+                dts = F.conv1d(dts.contiguous().view(B, -1, L), dt_projs_weight.view(K * D, -1, 1), groups=K)
+            else:
+                x_dbl = torch.einsum("b k d l, k c d -> b k c l", xs, x_proj_weight)
+                dts, Bs, Cs = torch.split(x_dbl, [R, N, N], dim=2)
+                dts = torch.einsum("b k r l, k d r -> b k d l", dts, dt_projs_weight)
 
-        xs = xs.view(B, -1, L)
-        dts = dts.contiguous().view(B, -1, L)
-        # (a float64 module — the tests' adjudicator runs — keeps float64; everything else is fp32 as in the reference)
-        f32 = (lambda t: t) if A_logs.dtype == torch.float64 else (lambda t: t.to(torch.float))
-        As = -torch.exp(f32(A_logs))  # (K*D, N)
-        Bs = Bs.contiguous().view(B, K, N, L)
-        Cs = Cs.contiguous().view(B, K, N, L)
-        Ds = f32(Ds)
-        delta_bias = f32(dt_projs_bias.view(-1))
-        if force_fp32:
-            xs, dts, Bs, Cs = xs.to(torch.float), dts.to(torch.float), Bs.to(torch.float), Cs.to(torch.float)
+            xs = xs.view(B, -1, L)
+            dts = dts.contiguous().view(B, -1, L)
+            # (a float64 module — the tests' adjudicator runs — keeps float64; everything else is fp32 as in the reference)
+            f32 = (lambda t: t) if A_logs.dtype == torch.float64 else (lambda t: t.to(torch.float))
+            As = -torch.exp(f32(A_logs))  # (K*D, N)
+            Bs = Bs.contiguous().view(B, K, N, L)
+            Cs = Cs.contiguous().view(B, K, N, L)
+            Ds = f32(Ds)
+            delta_bias = f32(dt_projs_bias.view(-1))
+            if force_fp32:
+                xs, dts, Bs, Cs = xs.to(torch.float), dts.to(torch.float), Bs.to(torch.float), Cs.to(torch.float)
 
-        ys = SelectiveScan.apply(xs, dts, As, Bs, Cs, Ds, delta_bias, delta_softplus, nrows, backnrows,
-                                 ssoflex).view(B, K, -1, H, W)
-        y = CrossMerge.apply(ys)
+            ys = SelectiveScan.apply(xs, dts, As, Bs, Cs, Ds, delta_bias, delta_softplus, nrows, backnrows,
+                                     ssoflex).view(B, K, -1, H, W)
+            y = CrossMerge.apply(ys)
         return y if merged_only else self._merge_norm(y, x, B, H, W, to_dtype)
 
     def _merge_norm(self, y, x, B, H, W, to_dtype):
@@ -400,18 +410,30 @@ class SS2D(nn.Module):
             raise RuntimeError("SS2D: vm_asr_amd has no CPU path (expected a CUDA/HIP tensor)")
         return self.act(self.conv2d(x))  # non-default kernel size / activation: MIOpen
 
+    def _core_kw(self):
+        """forward_corev2's keywords as `forward_core` will pass them; only a `partial` shows them (else {}: operators unknown)."""
+        return self.forward_core.keywords if isinstance(self.forward_core, partial) else {}
+
     def _fused_glue_ok(self, x):
-        """The HIP glue operators apply: GPU, channel-last, default operator set (no test hooks), z gate with SiLU,
-        3x3 conv, channel-last LayerNorm as out_norm."""
-        fc = self.forward_core
-        return (x.is_cuda and not self.channel_first and not self.disable_z and not self.disable_z_act and self._act_is_silu
+        """The HIP glue operators apply: channel-last, z gate with SiLU, 3x3 conv, channel-last LayerNorm as out_norm, the product
+        operators with softplus in `forward_core`, no test hook.  (tests/f64ref.py overrides this on the instance.)"""
+        kw = self._core_kw()
+        return (not self.channel_first and not self.disable_z and not self.disable_z_act and self._act_is_silu
                 and self.d_conv == 3 and self.out_norm_shape == "v0" and isinstance(self.out_norm, LayerNorm)
-                and getattr(self, "conv_act_fn", None) is None and isinstance(fc, partial)
-                and fc.keywords.get("SelectiveScan") is SelectiveScanCore and fc.keywords.get("CrossScan") is CrossScanHIP
-                and fc.keywords.get("CrossMerge") is CrossMergeHIP and fc.keywords.get("force_fp32", False)
-                # the fused cores are softplus / x_proj-as-einsum semantics only (forward_corev2's `hip_default` predicate): a
-                # forward_type that sets delta_softplus=False or no_einsum=True must take the operator chain
-                and fc.keywords.get("delta_softplus", True) and not fc.keywords.get("no_einsum", False))
+                and getattr(self, "conv_act_fn", None) is None
+                and product_ops_in_force(x.is_cuda, **kw) and kw.get("delta_softplus", True))
+
+    def _glue_path(self, x, pre_norm=None):
+        """forward()'s input and gate stages for the stream `x` in front of in_proj: "fused_in": LayerNorm + in_proj + chunk + SiLU(z)
+        + channel-first copy as one MFMA kernel (inproj.py), or "pre": the last three as one glue kernel (csrc/ss2d_glue.hip) — both
+        with the fused LayerNorm-gate behind the core —, or "module": the reference's sequence of modules."""
+        if x.dim() != 4 or not self._fused_glue_ok(x):
+            return "module"
+        L = x.shape[1] * x.shape[2]
+        if pre_norm is not None and _inproj.supported(x, pre_norm, self.in_proj) and _glue.supported(self.d_inner, L, torch.bfloat16):
+            return "fused_in"
+        xz_dtype = x.dtype if x.dtype == torch.float64 else _lib.autocast_dtype(x)    # in_proj's output (autocast leaves float64 alone)
+        return "pre" if _glue.supported(self.d_inner, L, xz_dtype) else "module"
 
     def _finish(self, y, residual):
         """out_proj (+ dropout) and — when the calling block handed over (stream, DropPath) — its stochastic-depth residual
@@ -427,39 +449,34 @@ class SS2D(nn.Module):
         """pre_norm: the block's LayerNorm (or nn.Identity) when the caller hands over the UN-normalised stream, so that
         LayerNorm + in_proj + chunk + SiLU(z) + the channel-first copy can run as one MFMA kernel (vm_asr_amd/inproj.py).
         residual: (stream, DropPath) of the calling VSSBlock — the result is then stream + drop_path(branch)."""
-        fused_in = (pre_norm is not None and x.dim() == 4 and self._fused_glue_ok(x) and _inproj.supported(x, pre_norm, self.in_proj)
-                    and _glue.supported(self.d_inner, x.shape[1] * x.shape[2], torch.bfloat16))
-        if not fused_in:
-            x = self.in_proj(x if pre_norm is None else pre_norm(x))
-        if fused_in or (x.dim() == 4 and self._fused_glue_ok(x) and _glue.supported(self.d_inner, x.shape[1] * x.shape[2], x.dtype)):
-            # chunk + SiLU(z) + layout copy as one kernel; LayerNorm + cast + gate (and the layout copy in front of
-            # them) as another (csrc/ss2d_glue.hip)
-            xT, sz = _inproj.fused_in_proj(x, pre_norm, self.in_proj) if fused_in else _glue.ss2d_pre(x)
-            u = self._conv_act(xT)
-            Bn, H, W = x.shape[0], x.shape[1], x.shape[2]
-            if (self.k_group == 4 and _ss2d.supported(self.d_state, self.dt_rank, self.d_inner, H, W)
-                    and _glue.pairs_supported(self.d_inner, H, W, sz.dtype)):
-                # fused core + LayerNorm-gate without the merged tensor: the core leaves its two pair outputs, ln_gate adds them
-                y02, y13 = _ss2d.ss2d_core_pairs(u, self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds)
-                y = _glue.ln_gate_pairs(y02, y13, sz, self.out_norm.weight, self.out_norm.bias, self.out_norm.eps)
-            else:
-                y = self.forward_core(u, merged_only=True)                        # (B, D, L) fp32
-                y = _glue.ln_gate(y, sz, self.out_norm.weight, self.out_norm.bias, self.out_norm.eps)
-            return self._finish(y, residual)
-        z = None
-        if not self.disable_z:
-            x, z = x.chunk(2, dim=(1 if self.channel_first else -1))
-            if not self.disable_z_act:
-                z = self.act(z)
-        if not self.channel_first:
-            x = x.permute(0, 3, 1, 2).contiguous()
-        if self.d_conv > 1:
-            x = self._conv_act(x)
+        glue = self._glue_path(x, pre_norm)
+        if glue == "fused_in":
+            u, z = _inproj.fused_in_proj(x, pre_norm, self.in_proj)
         else:
-            x = self.act(x)
-        y = self.forward_core(x)
-        if z is not None:
-            y = y * z
+            x = self.in_proj(x if pre_norm is None else pre_norm(x))
+            if glue == "pre":
+                u, z = _glue.ss2d_pre(x)
+            else:
+                u, z = x, None
+                if not self.disable_z:
+                    u, z = x.chunk(2, dim=(1 if self.channel_first else -1))
+                    if not self.disable_z_act:
+                        z = self.act(z)
+                if not self.channel_first:
+                    u = u.permute(0, 3, 1, 2).contiguous()
+        u = self._conv_act(u) if self.d_conv > 1 else self.act(u)
+        norm = self.out_norm
+        if glue == "module":
+            y = self.forward_core(u)
+            if z is not None:
+                y = y * z
+        elif core_path(self.d_state, self.dt_rank, self.d_inner, u.shape[2], u.shape[3], z.dtype, product_ops=True, delta_softplus=True,
+                       k_group=self.k_group, pairs_wanted=True) == "pairs":
+            # (the glue path being in force says both) without the merged tensor: the core leaves its two pair outputs, ln_gate adds them
+            y02, y13 = _ss2d.ss2d_core_pairs(u, self.x_proj_weight, self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds)
+            y = _glue.ln_gate_pairs(y02, y13, z, norm.weight, norm.bias, norm.eps)
+        else:
+            y = _glue.ln_gate(self.forward_core(u, merged_only=True), z, norm.weight, norm.bias, norm.eps)   # (B, D, L) fp32 in
         return self._finish(y, residual)
 
     forwardv2 = forward
@@ -502,14 +519,14 @@ class VSSBlock(nn.Module):
         if self.mlp_branch:
             if self.post_norm:
                 x = x + self.drop_path(self.norm2(self.mlp(x)))
-            elif _mlp.supported(x, self.norm2, self.mlp):
-                # LayerNorm + fc1 + GELU + fc2 + residual (+ the stochastic-depth scale) as ONE MFMA kernel (csrc/mlp.hip)
-                x = _mlp.fused_mlp_residual(x, self.norm2, self.mlp, self.drop_path._mask(x) if self.drop_path.active() else None)
-            elif isinstance(self.mlp, gMlp) and _gmlp.supported(x, self.norm2, self.mlp):
-                # the gated form (MODEL.VSSM.GMLP): LayerNorm + fc1 + u * GELU(z) + fc2 + residual as ONE MFMA kernel (csrc/gmlp.hip)
-                x = _gmlp.fused_gmlp_residual(x, self.norm2, self.mlp, self.drop_path._mask(x) if self.drop_path.active() else None)
             else:
-                x = self.drop_path.residual(x, self.mlp(self.norm2(x)))
+                # LayerNorm + fc1 + GELU (gMlp: u * GELU(z)) + fc2 + residual (+ the stochastic-depth scale) as ONE MFMA kernel, else modules
+                gated = isinstance(self.mlp, gMlp)
+                if (_gmlp if gated else _mlp).supported(x, self.norm2, self.mlp):
+                    fused = _gmlp.fused_gmlp_residual if gated else _mlp.fused_mlp_residual
+                    x = fused(x, self.norm2, self.mlp, self.drop_path._mask(x) if self.drop_path.active() else None)
+                else:
+                    x = self.drop_path.residual(x, self.mlp(self.norm2(x)))
         return x
 
     def forward(self, input: torch.Tensor):
