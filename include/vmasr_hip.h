@@ -662,7 +662,7 @@ int vmasr_mlp_bwd(const void *x, const void *gy, const float *gamma, const float
                   void *xn_aug, void *gys, void *act_aug, void *gpre, float *mean, float *rstd, int64_t rows, int32_t d,
                   int32_t x_dtype, vmasr_stream_t stream);
 
-/* ---- the gated Mlp branch (MODEL.VSSM.GMLP) as one MFMA kernel (vm_asr_amd/csrc/gmlp.hip) ---------------------------
+/* ---- the gated Mlp branch (MODEL.VSSM.GMLP) as one MFMA kernel (vm_asr_amd/csrc/mlp.hip, GATED) -----------------------
  * `x + DropPath(gMlp(LayerNorm(x)))` (model/vmamba.py:512-538, :1815): [u ; z] = fc1(LN(x)) with fc1: d -> 2 hidden,
  * y = x + scale * (fc2(u * GELU(z)) + b2), hidden = 4 d, d in {8,16,32,64} (vmasr_gmlp_supported).  Arguments, dtypes and
  * alignment as for vmasr_mlp_fwd / vmasr_mlp_bwd, with
@@ -890,7 +890,7 @@ enum {
     VMASR_K_WEIGHT_T,           /* (n, Cout, k, Cin) fp32 weight operand -> the input gradient's (n, Cin, k*Cout) operand, bf16 pair or fp32 */
     VMASR_K_MLP_FWD,            /* LayerNorm + fc1 + GELU + fc2 + residual of a VSS block as one MFMA kernel */
     VMASR_K_MLP_BWD,
-    VMASR_K_GMLP_FWD,           /* the gated form: LayerNorm + fc1 + u * GELU(z) + fc2 + residual as one MFMA kernel (csrc/gmlp.hip) */
+    VMASR_K_GMLP_FWD,           /* the gated form: LayerNorm + fc1 + u * GELU(z) + fc2 + residual as one MFMA kernel (csrc/mlp.hip) */
     VMASR_K_GMLP_BWD,
     VMASR_K_INPROJ_FWD,         /* LayerNorm + in_proj + chunk + SiLU(z) + channel-first copy of a VSS block's SS2D as one MFMA kernel */
     VMASR_K_INPROJ_BWD,

@@ -1,4 +1,4 @@
-"""The fused gated-Mlp branch (vm_asr_amd/csrc/gmlp.hip: LayerNorm + fc1 + u * GELU(z) + fc2 + residual as one MFMA kernel, and its
+"""The fused gated-Mlp branch (vm_asr_amd/csrc/mlp.hip, GATED: LayerNorm + fc1 + u * GELU(z) + fc2 + residual as one MFMA kernel, and its
 backward; binding vm_asr_amd/gmlp.py) against the composition of the same steps (model/vmamba.py:512-538, :1832-1837) written out
 below — evaluated in float64 as the adjudicator and, as the yardstick for "bf16 accuracy", by torch's own bf16 autocast of the
 very same lines on the GPU.  Error of a quantity = max-abs difference over the float64 answer's max-abs."""

@@ -1,7 +1,7 @@
 """Fused Mlp branch (csrc/mlp.hip) vs the unfused module path (LayerNorm -> Linear -> GELU -> Linear -> add, hipBLASLt + ATen +
 ln.hip) at the generator's shapes (B = $B, default 4), bf16 autocast: device time per call, forward and forward+backward,
 REP calls captured in a HIP graph and replayed (dev tool).
---gated: the gated Mlp (MODEL.VSSM.GMLP; csrc/gmlp.hip, vm_asr_amd/gmlp.py) against its module path instead."""
+--gated: the gated Mlp (MODEL.VSSM.GMLP; csrc/mlp.hip's GATED kernels, vm_asr_amd/gmlp.py) against its module path instead."""
 import os
 import sys
 

@@ -4,8 +4,8 @@
 //                                                         :483-509 (Mlp), timm DropPath (s = per-sample keep mask / keep)
 //
 // for the residual stream x (rows, d) fp32 or bf16 (under autocast the stream is bf16 behind every PatchMerging /
-// skip convolution, fp32 elsewhere) with d in {8, 16, 32, 64, 128} and hidden = 4 d — every Mlp of every shipped
-// config except the d_model = 1 block (csrc/linear.hip) and dims-32's deepest stage.  Under bf16 autocast the reference
+// skip convolution, fp32 elsewhere) with d in {8, 16, 32, 64} and hidden = 4 d — every Mlp of every shipped
+// config except the d_model = 1 block (csrc/linear.hip) and the stages wider than 64 (supported_d below).  Under bf16 autocast the reference
 // runs this as LayerNorm -> cast -> GEMM -> bias -> GELU -> GEMM -> bias -> add: 6-7 launches forward and ~13 backward
 // per block over tensors of 0.1-8 MB, i.e. at the launch-latency floor (28 blocks per generator pass).
 //
@@ -27,6 +27,17 @@
 //
 // Numerics: bf16 operands, fp32 accumulation — the reference's autocast dtype; fc1's output is NOT rounded to bf16 before
 // GELU and fc2's not before the residual add (the reference rounds both), so the result is closer to the fp32 model.
+//
+// The GATED Mlp (MODEL.VSSM.GMLP; model/vmamba.py:512-538 gMlp, :1815) is the same kernel body, template flag GATED:
+//     [u ; z] = fc1(LayerNorm(x))   (fc1: d -> 2 * hidden; u = the first `hidden` rows of fc1.weight, z = the second)
+//     y = x + s * fc2(u * GELU(z))
+// Per hidden tile t the wave forms TWO accumulator tiles — rows 32 t.. (u) and rows 4 d + 32 t.. (z) of W1 against the same
+// operand xn^T.  Both have the same layout, so the gate u * GELU(z) is a lane-local product of corresponding registers; it is
+// taken in fp32 on the un-rounded fc1 outputs, rounded ONCE to bf16 and fed to fc2 exactly as GELU(h) is.  Backward:
+//     du = dact * GELU(z),   dz = dact * u * GELU'(z),   dxn^T = W1u^T . du^T + W1z^T . dz^T
+// (two MFMA contributions per k-step, from the u and then the z columns of w1t (d, 8 d)); gpre = [du | dz] (rows, 8 d) and
+// act_aug = [u * GELU(z) | 1 0..].  The body loops over its NP = 1 or 2 pre-activation tiles; GATED itself is asked only where
+// the activation and its gradients are formed.
 #include "mlp_tile.h"
 
 namespace vmasr {
@@ -35,8 +46,8 @@ namespace {
 struct MlpArgs {
     const void *x;                  // (rows, D) fp32 or bf16 (the residual stream's dtype: TX)
     const float *gamma, *beta;      // (D)
-    const bf16_t *w1;               // (4D, D)   fc1.weight
-    const float *b1;                // (4D)
+    const bf16_t *w1;               // (4D, D)   fc1.weight             (GATED: 8D rows, 0 .. 4D-1 = u, 4D .. 8D-1 = z)
+    const float *b1;                // (4D)                             (GATED: 8D)
     const bf16_t *w2;               // (D, 4D)   fc2.weight
     const float *b2;                // (D)
     const float *scale;             // per-sample residual scale (DropPath) or null
@@ -46,25 +57,28 @@ struct MlpArgs {
     float eps;
     // backward only
     const void *gy;                 // (rows, D) TX
-    const bf16_t *w1t;              // (D, 4D)   fc1.weight^T
+    const bf16_t *w1t;              // (D, 4D)   fc1.weight^T           (GATED: 8D columns)
     const bf16_t *w2t;              // (4D, D)   fc2.weight^T
     bf16_t *dxn;                    // (rows, D)
     bf16_t *xn_aug;                 // (rows, D + 8):  xn | 1 0 0 0 0 0 0 0
     bf16_t *gys;                    // (rows, D):      s * gy
-    bf16_t *act_aug;                // (rows, 4D + 8): GELU(h) | 1 0 ...
-    bf16_t *gpre;                   // (rows, 4D)
+    bf16_t *act_aug;                // (rows, 4D + 8): GELU(h) | 1 0 ...   (GATED: u * GELU(z) | 1 0 ...)
+    bf16_t *gpre;                   // (rows, 4D)                       (GATED: 8D, du | dz)
     float *mean, *rstd;             // (rows)
     unsigned *det = nullptr;        // deterministic mode (common.h): the hidden-split waves add their partial tiles to LDS in wave order
 };
 
-template <int D, typename TX, int HS>
-__global__ __launch_bounds__(HS > 4 ? 64 * HS : 256) void mlp_fwd_kernel(const MlpArgs a) {
+template <int D, typename TX, int HS, bool GATED>
+__global__ __launch_bounds__(256) void mlp_fwd_kernel(const MlpArgs a) {
     constexpr int KS = (D + 15) / 16, HD = 4 * D, HT = HD / 32, OT = (D + 31) / 32;
+    constexpr int NP = GATED ? 2 : 1;                            // pre-activation tiles per hidden tile: h, or u and z
     constexpr int TPW = HS > 1 ? 1 : 4;                          // row tiles per workgroup
+    static_assert(HS == 1 || HS == 4, "a workgroup is four waves: four row tiles, or one row tile split over the hidden tiles");
     __shared__ float s_out[HS > 1 ? OT * 32 * 32 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int split = HS > 1 ? wave : 0;
+    const bf16_t *const w1[2] = {a.w1, a.w1 + (size_t)HD * D};          // the rows of h or u; the rows of z (GATED only)
     for (long tile = (long)blockIdx.x * TPW + (HS > 1 ? 0 : wave); tile * 32 < a.rows; tile += (long)gridDim.x * TPW) {
         const long row = tile * 32 + r;
         const bool ok = row < a.rows;
@@ -87,16 +101,28 @@ __global__ __launch_bounds__(HS > 4 ? 64 * HS : 256) void mlp_fwd_kernel(const M
         }
 #pragma unroll 1
         for (int t = split; t < HT; t += HS) {
-            const f32x16 hacc = hidden_tile<D, KS>(a.w1, t, r, h, xn);
+            f32x16 hacc[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) hacc[p] = hidden_tile<D, KS>(w1[p], t, r, h, xn);
             bf16x8 act[2];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const float4 bq = *reinterpret_cast<const float4 *>(a.b1 + 32 * t + 8 * g + 4 * h);
-                const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
+                const int hid0 = 32 * t + 8 * g + 4 * h;
+                float bb[NP][4];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const float4 bq = *reinterpret_cast<const float4 *>(a.b1 + p * HD + hid0);
+                    bb[p][0] = bq.x; bb[p][1] = bq.y; bb[p][2] = bq.z; bb[p][3] = bq.w;
+                }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const float v = hacc[4 * g + c] + bb[c];
-                    act[g >> 1][4 * (g & 1) + c] = (bf16_t)(0.5f * v * (1.f + erff(v * kRsqrt2)));
+                    float pre[NP];                                                       // fc1's output: h, or u and z
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) pre[p] = hacc[p][4 * g + c] + bb[p][c];
+                    const float v = pre[NP - 1];                                         // GELU's argument: h, or z
+                    const float gel = 0.5f * v * (1.f + erff(v * kRsqrt2));
+                    if constexpr (GATED) act[g >> 1][4 * (g & 1) + c] = (bf16_t)(pre[0] * gel);
+                    else act[g >> 1][4 * (g & 1) + c] = (bf16_t)gel;
                 }
             }
 #pragma unroll
@@ -133,14 +159,17 @@ __global__ __launch_bounds__(HS > 4 ? 64 * HS : 256) void mlp_fwd_kernel(const M
     }
 }
 
-template <int D, typename TX, int HS>
-__global__ __launch_bounds__(HS > 4 ? 64 * HS : 256) void mlp_bwd_kernel(const MlpArgs a) {
+template <int D, typename TX, int HS, bool GATED>
+__global__ __launch_bounds__(256) void mlp_bwd_kernel(const MlpArgs a) {
     constexpr int KS = (D + 15) / 16, HD = 4 * D, HT = HD / 32, OT = (D + 31) / 32;
+    constexpr int NP = GATED ? 2 : 1;                            // as in the forward; gpre and w1t have NP * HD columns
     constexpr int TPW = HS > 1 ? 1 : 4;
+    static_assert(HS == 1 || HS == 4, "a workgroup is four waves");
     __shared__ float s_out[HS > 1 ? OT * 32 * 32 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int split = HS > 1 ? wave : 0;
+    const bf16_t *const w1[2] = {a.w1, a.w1 + (size_t)HD * D};          // the rows of h or u; the rows of z (GATED only)
     for (long tile = (long)blockIdx.x * TPW + (HS > 1 ? 0 : wave); tile * 32 < a.rows; tile += (long)gridDim.x * TPW) {
         const long row = tile * 32 + r;
         const bool ok = row < a.rows;
@@ -183,36 +212,57 @@ __global__ __launch_bounds__(HS > 4 ? 64 * HS : 256) void mlp_bwd_kernel(const M
         }
 #pragma unroll 1
         for (int t = split; t < HT; t += HS) {
-            const f32x16 hacc = hidden_tile<D, KS>(a.w1, t, r, h, xn);
+            f32x16 hacc[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) hacc[p] = hidden_tile<D, KS>(w1[p], t, r, h, xn);
             const f32x16 dacc = hidden_tile<D, KS>(a.w2t, t, r, h, gyf);   // dact^T = W2^T[32 t .., :] . (s gy)^T
-            bf16x8 gp[2];
+            bf16x8 gp[NP][2];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int hid0 = 32 * t + 8 * g + 4 * h;
-                const float4 bq = *reinterpret_cast<const float4 *>(a.b1 + hid0);
-                const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
-                float av[4], gv[4];
+                float bb[NP][4];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const float4 bq = *reinterpret_cast<const float4 *>(a.b1 + p * HD + hid0);
+                    bb[p][0] = bq.x; bb[p][1] = bq.y; bb[p][2] = bq.z; bb[p][3] = bq.w;
+                }
+                float av[4], gv[NP][4];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const float v = hacc[4 * g + c] + bb[c];
+                    float pre[NP];                                                       // fc1's output: h, or u and z
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) pre[p] = hacc[p][4 * g + c] + bb[p][c];
+                    const float v = pre[NP - 1];                                         // GELU's argument: h, or z
                     const float cdf = 0.5f * (1.f + erff(v * kRsqrt2));
                     const float pdf = kInvSqrt2Pi * __expf(-0.5f * v * v);
-                    av[c] = v * cdf;
-                    gv[c] = dacc[4 * g + c] * fmaf(v, pdf, cdf);
-                    gp[g >> 1][4 * (g & 1) + c] = (bf16_t)gv[c];
+                    const float gel = v * cdf, da = dacc[4 * g + c];
+                    if constexpr (GATED) {
+                        av[c] = pre[0] * gel;
+                        gv[0][c] = da * gel;
+                        gv[1][c] = da * pre[0] * fmaf(v, pdf, cdf);
+                    } else {
+                        av[c] = gel;
+                        gv[0][c] = da * fmaf(v, pdf, cdf);
+                    }
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) gp[p][g >> 1][4 * (g & 1) + c] = (bf16_t)gv[p][c];
                 }
                 if (ok) {
                     store_bf16x4(a.act_aug + row * (HD + 8) + hid0, av[0], av[1], av[2], av[3]);
-                    store_bf16x4(a.gpre + row * HD + hid0, gv[0], gv[1], gv[2], gv[3]);
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+                        store_bf16x4(a.gpre + row * (NP * HD) + p * HD + hid0, gv[p][0], gv[p][1], gv[p][2], gv[p][3]);
                 }
             }
 #pragma unroll
             for (int u = 0; u < OT; ++u) {
                 const int f = 32 * u + r;
-                const bf16_t *wr = a.w1t + (size_t)f * HD;
+                const bf16_t *wr = a.w1t + (size_t)f * (NP * HD);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2)
-                    dx[u] = mfma_bf16(perm_frag(wr, 32 * t + 16 * s2 + 4 * h, f < D), gp[s2], dx[u]);
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+                        dx[u] = mfma_bf16(perm_frag(wr, p * HD + 32 * t + 16 * s2 + 4 * h, f < D), gp[p][s2], dx[u]);
             }
         }
         if constexpr (HS > 1) {
@@ -366,29 +416,79 @@ __global__ __launch_bounds__(256) void inproj_kernel(const InProjArgs a) {
     }
 }
 
-// d = 128 (1 024 rows at batch 4) is built but not offered: with 16 hidden tiles per row tile and 32 row tiles the kernel is a
-// chain of dependent weight-fragment loads (62 us forward against 30 us for the hipBLASLt path, tools/bench_mlp.py); it needs
-// the weights staged through LDS for the workgroup — until then the module path runs there.
+// d = 128 (1 024 rows at batch 4) is not offered, and no longer instantiated: with 16 hidden tiles per row tile and 32 row tiles
+// the kernel is a chain of dependent weight-fragment loads (62 us forward against 30 us for the hipBLASLt path,
+// tools/bench_mlp.py) and an 8-wave hidden split spills.  It needs the weights staged through LDS for the workgroup; until
+// then the module path runs there.
 bool supported_d(int d) { return d == 8 || d == 16 || d == 32 || d == 64; }
 
-template <bool BWD, typename TX>
-int launch(const MlpArgs &a, int d, hipStream_t st) {
+template <bool BWD, typename TX, bool GATED>
+int launch(const MlpArgs &a, int d, int kid, const char *name, hipStream_t st) {
     const double sx = sizeof(TX);
-    // bytes: forward x in + y out; backward x, gy in + dxn, xn, gys (2 B) + act, gpre (2 B x 4 d) out
-    const double bytes = (double)a.rows * d * (BWD ? 2 * sx + 2.0 * 3 + 2.0 * 8 : 2 * sx);
+    // bytes: forward x in + y out; backward x, gy in + dxn, xn, gys (2 B) + act (2 B x 4 d) + gpre (2 B x 4 d, GATED: 8 d) out
+    const double bytes = (double)a.rows * d * (BWD ? 2 * sx + 2.0 * 3 + 2.0 * (GATED ? 12 : 8) : 2 * sx);
     // waves per row tile: 1 while the rows alone fill the chip (d <= 32: >= 16 384 rows at batch 4), hidden-split below that
 #define VMASR_MLP_CASE(DD, HS)                                                                                          \
     case DD: {                                                                                                          \
-        const dim3 grid(grid_for(a.rows, HS > 1 ? 1 : 4)), block(HS > 4 ? 64 * HS : 256);                              \
-        if (BWD) VMASR_LAUNCH(VMASR_K_MLP_BWD, bytes, (mlp_bwd_kernel<DD, TX, HS>), grid, block, 0, st, a);            \
-        else VMASR_LAUNCH(VMASR_K_MLP_FWD, bytes, (mlp_fwd_kernel<DD, TX, HS>), grid, block, 0, st, a);                \
+        const dim3 grid(grid_for(a.rows, HS > 1 ? 1 : 4)), block(256);                                                  \
+        if (BWD) VMASR_LAUNCH(kid, bytes, (mlp_bwd_kernel<DD, TX, HS, GATED>), grid, block, 0, st, a);                  \
+        else VMASR_LAUNCH(kid, bytes, (mlp_fwd_kernel<DD, TX, HS, GATED>), grid, block, 0, st, a);                      \
     } break;
     switch (d) {
-        VMASR_MLP_CASE(8, 1) VMASR_MLP_CASE(16, 1) VMASR_MLP_CASE(32, 1) VMASR_MLP_CASE(64, 4) VMASR_MLP_CASE(128, 8)
-        default: set_error("mlp: unsupported width %d", d); return VMASR_EINVAL;
+        VMASR_MLP_CASE(8, 1) VMASR_MLP_CASE(16, 1) VMASR_MLP_CASE(32, 1) VMASR_MLP_CASE(64, 4)
+        default: set_error("%s: unsupported width %d", name, d); return VMASR_EINVAL;
     }
 #undef VMASR_MLP_CASE
-    return check_launch(BWD ? "mlp_bwd" : "mlp_fwd");
+    return check_launch(name);
+}
+
+template <bool BWD>
+int launch_form(const MlpArgs &a, int d, int x_dtype, bool gated, int kid, const char *name, vmasr_stream_t stream) {
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (gated) return x_dtype == VMASR_F32 ? launch<BWD, float, true>(a, d, kid, name, st) : launch<BWD, bf16_t, true>(a, d, kid, name, st);
+    return x_dtype == VMASR_F32 ? launch<BWD, float, false>(a, d, kid, name, st) : launch<BWD, bf16_t, false>(a, d, kid, name, st);
+}
+
+// The entry points of both forms: `gated` picks the kernels, `kid` the profile row and deterministic-mode ticket
+// (VMASR_K_MLP_* / VMASR_K_GMLP_*), `name` ("mlp_fwd", "gmlp_fwd", ...) the prefix of every message.
+int mlp_fwd(bool gated, int kid, const char *name, const void *x, const float *gamma, const float *beta, float eps, const void *w1,
+            const float *b1, const void *w2, const float *b2, const float *scale, int32_t rows_per_sample, void *y, int64_t rows,
+            int32_t d, int32_t x_dtype, vmasr_stream_t stream) {
+    VMASR_REQUIRE(x_dtype == VMASR_F32 || x_dtype == VMASR_BF16, VMASR_EINVAL, "%s: x must be fp32 or bf16", name);
+    VMASR_REQUIRE(x && gamma && beta && w1 && b1 && w2 && b2 && y, VMASR_EINVAL, "%s: null tensor", name);
+    VMASR_REQUIRE(supported_d(d) && rows > 0, VMASR_EINVAL, "%s: need d in {8,16,32,64} (got %d) and rows > 0", name, d);
+    VMASR_REQUIRE(!scale || rows_per_sample > 0, VMASR_EINVAL, "%s: rows_per_sample must be positive with a scale vector", name);
+    VMASR_REQUIRE(aligned_to(x, 16) && aligned_to(y, 16) && aligned_to(w1, 16) && aligned_to(w2, 16) && aligned_to(b1, 16) &&
+                      aligned_to(b2, 16), VMASR_EINVAL, "%s: tensors must be 16-byte aligned", name);
+    MlpArgs a{};
+    a.det = det_ticket(kid);
+    a.x = x; a.gamma = gamma; a.beta = beta; a.eps = eps;
+    a.w1 = static_cast<const bf16_t *>(w1); a.b1 = b1; a.w2 = static_cast<const bf16_t *>(w2); a.b2 = b2;
+    a.scale = scale; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; a.y = y; a.rows = rows;
+    return launch_form<false>(a, d, x_dtype, gated, kid, name, stream);
+}
+
+int mlp_bwd(bool gated, int kid, const char *name, const void *x, const void *gy, const float *gamma, const float *beta, float eps,
+            const void *w1, const void *w1t, const float *b1, const void *w2t, const float *scale, int32_t rows_per_sample,
+            void *dxn, void *xn_aug, void *gys, void *act_aug, void *gpre, float *mean, float *rstd, int64_t rows, int32_t d,
+            int32_t x_dtype, vmasr_stream_t stream) {
+    VMASR_REQUIRE(x_dtype == VMASR_F32 || x_dtype == VMASR_BF16, VMASR_EINVAL, "%s: x / gy must be fp32 or bf16", name);
+    VMASR_REQUIRE(x && gy && gamma && beta && w1 && w1t && b1 && w2t && dxn && xn_aug && gys && act_aug && gpre && mean && rstd,
+                  VMASR_EINVAL, "%s: null tensor", name);
+    VMASR_REQUIRE(supported_d(d) && rows > 0, VMASR_EINVAL, "%s: need d in {8,16,32,64} (got %d) and rows > 0", name, d);
+    VMASR_REQUIRE(!scale || rows_per_sample > 0, VMASR_EINVAL, "%s: rows_per_sample must be positive with a scale vector", name);
+    VMASR_REQUIRE(aligned_to(x, 16) && aligned_to(gy, 16) && aligned_to(w1, 16) && aligned_to(w1t, 16) && aligned_to(w2t, 16) &&
+                      aligned_to(b1, 16) && aligned_to(dxn, 16) && aligned_to(xn_aug, 16) && aligned_to(gys, 16) &&
+                      aligned_to(act_aug, 16) && aligned_to(gpre, 16), VMASR_EINVAL, "%s: tensors must be 16-byte aligned", name);
+    MlpArgs a{};
+    a.det = det_ticket(kid);
+    a.x = x; a.gy = gy; a.gamma = gamma; a.beta = beta; a.eps = eps;
+    a.w1 = static_cast<const bf16_t *>(w1); a.w1t = static_cast<const bf16_t *>(w1t); a.b1 = b1;
+    a.w2t = static_cast<const bf16_t *>(w2t);
+    a.scale = scale; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; a.rows = rows;
+    a.dxn = static_cast<bf16_t *>(dxn); a.xn_aug = static_cast<bf16_t *>(xn_aug); a.gys = static_cast<bf16_t *>(gys);
+    a.act_aug = static_cast<bf16_t *>(act_aug); a.gpre = static_cast<bf16_t *>(gpre); a.mean = mean; a.rstd = rstd;
+    return launch_form<true>(a, d, x_dtype, gated, kid, name, stream);
 }
 
 }  // namespace
@@ -397,47 +497,34 @@ int launch(const MlpArgs &a, int d, hipStream_t st) {
 using namespace vmasr;
 
 VMASR_EXPORT int vmasr_mlp_supported(int32_t d, int32_t hidden) { return supported_d(d) && hidden == 4 * d; }
+VMASR_EXPORT int vmasr_gmlp_supported(int32_t d, int32_t hidden) { return supported_d(d) && hidden == 4 * d; }
 
 VMASR_EXPORT int vmasr_mlp_fwd(const void *x, const float *gamma, const float *beta, float eps, const void *w1, const float *b1,
                                const void *w2, const float *b2, const float *scale, int32_t rows_per_sample, void *y,
                                int64_t rows, int32_t d, int32_t x_dtype, vmasr_stream_t stream) {
-    VMASR_REQUIRE(x_dtype == VMASR_F32 || x_dtype == VMASR_BF16, VMASR_EINVAL, "mlp_fwd: x must be fp32 or bf16");
-    VMASR_REQUIRE(x && gamma && beta && w1 && b1 && w2 && b2 && y, VMASR_EINVAL, "mlp_fwd: null tensor");
-    VMASR_REQUIRE(supported_d(d) && rows > 0, VMASR_EINVAL, "mlp_fwd: need d in {8,16,32,64} (got %d) and rows > 0", d);
-    VMASR_REQUIRE(!scale || rows_per_sample > 0, VMASR_EINVAL, "mlp_fwd: rows_per_sample must be positive with a scale vector");
-    VMASR_REQUIRE(aligned_to(x, 16) && aligned_to(y, 16) && aligned_to(w1, 16) && aligned_to(w2, 16) && aligned_to(b1, 16) &&
-                      aligned_to(b2, 16), VMASR_EINVAL, "mlp_fwd: tensors must be 16-byte aligned");
-    MlpArgs a{};
-    a.det = det_ticket(VMASR_K_MLP_FWD);
-    a.x = x; a.gamma = gamma; a.beta = beta; a.eps = eps;
-    a.w1 = static_cast<const bf16_t *>(w1); a.b1 = b1; a.w2 = static_cast<const bf16_t *>(w2); a.b2 = b2;
-    a.scale = scale; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; a.y = y; a.rows = rows;
-    return x_dtype == VMASR_F32 ? launch<false, float>(a, d, static_cast<hipStream_t>(stream))
-                                : launch<false, bf16_t>(a, d, static_cast<hipStream_t>(stream));
+    return mlp_fwd(false, VMASR_K_MLP_FWD, "mlp_fwd", x, gamma, beta, eps, w1, b1, w2, b2, scale, rows_per_sample, y, rows, d, x_dtype, stream);
+}
+
+VMASR_EXPORT int vmasr_gmlp_fwd(const void *x, const float *gamma, const float *beta, float eps, const void *w1, const float *b1,
+                                const void *w2, const float *b2, const float *scale, int32_t rows_per_sample, void *y,
+                                int64_t rows, int32_t d, int32_t x_dtype, vmasr_stream_t stream) {
+    return mlp_fwd(true, VMASR_K_GMLP_FWD, "gmlp_fwd", x, gamma, beta, eps, w1, b1, w2, b2, scale, rows_per_sample, y, rows, d, x_dtype, stream);
 }
 
 VMASR_EXPORT int vmasr_mlp_bwd(const void *x, const void *gy, const float *gamma, const float *beta, float eps, const void *w1,
                                const void *w1t, const float *b1, const void *w2t, const float *scale, int32_t rows_per_sample,
                                void *dxn, void *xn_aug, void *gys, void *act_aug, void *gpre, float *mean, float *rstd,
                                int64_t rows, int32_t d, int32_t x_dtype, vmasr_stream_t stream) {
-    VMASR_REQUIRE(x_dtype == VMASR_F32 || x_dtype == VMASR_BF16, VMASR_EINVAL, "mlp_bwd: x / gy must be fp32 or bf16");
-    VMASR_REQUIRE(x && gy && gamma && beta && w1 && w1t && b1 && w2t && dxn && xn_aug && gys && act_aug && gpre && mean && rstd,
-                  VMASR_EINVAL, "mlp_bwd: null tensor");
-    VMASR_REQUIRE(supported_d(d) && rows > 0, VMASR_EINVAL, "mlp_bwd: need d in {8,16,32,64} (got %d) and rows > 0", d);
-    VMASR_REQUIRE(!scale || rows_per_sample > 0, VMASR_EINVAL, "mlp_bwd: rows_per_sample must be positive with a scale vector");
-    VMASR_REQUIRE(aligned_to(x, 16) && aligned_to(gy, 16) && aligned_to(w1, 16) && aligned_to(w1t, 16) && aligned_to(w2t, 16) &&
-                      aligned_to(b1, 16) && aligned_to(dxn, 16) && aligned_to(xn_aug, 16) && aligned_to(gys, 16) &&
-                      aligned_to(act_aug, 16) && aligned_to(gpre, 16), VMASR_EINVAL, "mlp_bwd: tensors must be 16-byte aligned");
-    MlpArgs a{};
-    a.det = det_ticket(VMASR_K_MLP_BWD);
-    a.x = x; a.gy = gy; a.gamma = gamma; a.beta = beta; a.eps = eps;
-    a.w1 = static_cast<const bf16_t *>(w1); a.w1t = static_cast<const bf16_t *>(w1t); a.b1 = b1;
-    a.w2t = static_cast<const bf16_t *>(w2t);
-    a.scale = scale; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; a.rows = rows;
-    a.dxn = static_cast<bf16_t *>(dxn); a.xn_aug = static_cast<bf16_t *>(xn_aug); a.gys = static_cast<bf16_t *>(gys);
-    a.act_aug = static_cast<bf16_t *>(act_aug); a.gpre = static_cast<bf16_t *>(gpre); a.mean = mean; a.rstd = rstd;
-    return x_dtype == VMASR_F32 ? launch<true, float>(a, d, static_cast<hipStream_t>(stream))
-                                : launch<true, bf16_t>(a, d, static_cast<hipStream_t>(stream));
+    return mlp_bwd(false, VMASR_K_MLP_BWD, "mlp_bwd", x, gy, gamma, beta, eps, w1, w1t, b1, w2t, scale, rows_per_sample, dxn, xn_aug, gys,
+                   act_aug, gpre, mean, rstd, rows, d, x_dtype, stream);
+}
+
+VMASR_EXPORT int vmasr_gmlp_bwd(const void *x, const void *gy, const float *gamma, const float *beta, float eps, const void *w1,
+                                const void *w1t, const float *b1, const void *w2t, const float *scale, int32_t rows_per_sample,
+                                void *dxn, void *xn_aug, void *gys, void *act_aug, void *gpre, float *mean, float *rstd,
+                                int64_t rows, int32_t d, int32_t x_dtype, vmasr_stream_t stream) {
+    return mlp_bwd(true, VMASR_K_GMLP_BWD, "gmlp_bwd", x, gy, gamma, beta, eps, w1, w1t, b1, w2t, scale, rows_per_sample, dxn, xn_aug, gys,
+                   act_aug, gpre, mean, rstd, rows, d, x_dtype, stream);
 }
 
 template <bool BWD, typename TX>

@@ -1,5 +1,5 @@
 // mlp_tile.h — the device helpers of the wave-owns-32-rows transposed-MFMA scheme (v_mfma_f32_32x32x16_bf16), shared by the
-// VSS-block kernels of mlp.hip (Mlp, in_proj, out_proj) and gmlp.hip (gated Mlp).  The scheme itself is described at the top of
+// VSS-block kernels of mlp.hip (Mlp plain and gated, in_proj, out_proj).  The scheme itself is described at the top of
 // mlp.hip; every function here is per-lane, needs no LDS and no barrier (lds_accumulate excepted: the hidden-split epilogue).
 #pragma once
 #include "common.h"

@@ -1,4 +1,4 @@
-"""The gated Mlp branch of a VSSBlock (MODEL.VSSM.GMLP) as one HIP operator on the matrix cores (vm_asr_amd/csrc/gmlp.hip):
+"""The gated Mlp branch of a VSSBlock (MODEL.VSSM.GMLP) as one HIP operator on the matrix cores (vm_asr_amd/csrc/mlp.hip, GATED):
 
     fused_gmlp_residual(x, norm2, mlp, scale=None)  ==  x + scale * mlp(norm2(x))
 
