@@ -475,6 +475,29 @@ int32_t vmasr_adamw_chunk(void);
 int vmasr_adamw_step(const vmasr_adamw_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems, const float *lr,
                      const float *step, float beta1, float beta2, float eps, vmasr_stream_t stream);
 
+/* Gradient guard (csrc/gradnorm.hip): global L2 norm, clip coefficient and non-finite flag of many gradient tensors, on the device.
+ * `segments` is a DEVICE array of (pointer, element count), any alignment; `chunks` a DEVICE array of (segment index, chunk index)
+ * int32 pairs, one per workgroup, chunk = vmasr_adamw_chunk() elements (the table vmasr_adamw_step takes); total_elems = sum of n.
+ * `state`: DEVICE floats: [0] the L2 norm over all segments, [1] min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_;
+ * 1 when max_norm <= 0: no clipping), [2] 1.0 if any ELEMENT is inf / NaN else 0.0, [3] a running count of the calls that set [2]
+ * (incremented, never reset: zero it once; a float, exact up to 2^24), and a fifth, derived one: [4] = 1 - [2], what an optimiser's
+ * step counters advance by.  workspace: vmasr_grad_norm_workspace(nchunks) bytes of scratch, 8-byte aligned.
+ * Two launches, no host read, no float atomics: the same data gives the same four bit patterns on every call. */
+typedef struct vmasr_grad_segment {
+    const float *ptr;
+    int64_t n;
+} vmasr_grad_segment;
+size_t vmasr_grad_norm_workspace(int32_t nchunks);
+int vmasr_grad_norm(const vmasr_grad_segment *segments, const int32_t *chunks, int32_t nchunks, int64_t total_elems, float max_norm,
+                    float *state, void *workspace, size_t ws_bytes, vmasr_stream_t stream);
+/* vmasr_adamw_step behind that state (the same kernel body): every gradient element is multiplied by state[1] as it is read (the
+ * gradient buffer is left as it is); when state[2] != 0 nothing is written: p, m, v and the shadows stay bit-identical.
+ * step_counters (may be NULL with ncounters 0): a DEVICE array of pointers to fp32 step counters, each advanced by state[4] BEFORE the
+ * update reads `step` (usually one of them): a step that is not taken does not count. */
+int vmasr_adamw_step_guarded(const vmasr_adamw_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems, const float *lr,
+                             const float *step, float beta1, float beta2, float eps, const float *state, float *const *step_counters,
+                             int32_t ncounters, vmasr_stream_t stream);
+
 /* Spectrally normalised weights of one discriminator layer, stacked for the batched pass (model/discriminator.py:26-45:
  * spectral_norm around every convolution; sigma, u, v from the power iteration are constants for autograd):
  *   fwd: out (n, N, k*Cin) with out[s, o, j*Cin + c] = W_s[o, c, j] / sigma_s   (W_s: (N, Cin, k) fp32, HOST array of n pointers)
@@ -921,6 +944,7 @@ enum {
     VMASR_K_DCONV1D_REDUCE,     /* the ordered sum of their K-slab partials + the epilogue (no float atomics) */
     VMASR_K_DCONV1D_WGRAD,      /* its weight / bias gradient: whole-K tiles, or (b, t) slabs into a workspace */
     VMASR_K_DCONV1D_WGRAD_REDUCE, /* the ordered sum of those slabs */
+    VMASR_K_GRAD_NORM,          /* gradient guard: per-chunk sums of squares + non-finite flags, ordered finish (csrc/gradnorm.hip) */
     VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };

@@ -57,6 +57,10 @@ def parse_option(argv=None):
     p.add_argument("--segment-batch", type=int, default=1, help="--inference: segments of a long file per generator call")
     p.add_argument("--step-metrics", action="store_true",
                    help="metrics on every step / clip through the fused kernel (Trainer step_metrics, Tester fused_metrics)")
+    p.add_argument("--skip-nonfinite", action="store_true",
+                   help="do not take an optimiser step whose gradients hold an inf or a NaN (device-side gradient guard, one per optimiser)")
+    p.add_argument("--clip-grad", type=float, default=None, metavar="FLOAT",
+                   help="clip each optimiser's gradients to this global L2 norm on the device (implies the guard of --skip-nonfinite)")
     args = p.parse_args(argv)
     if args.data_path and args.synthetic is not None:
         p.error("--data-path and --synthetic exclude each other")
@@ -146,7 +150,7 @@ def main(args, config):
     sched = {k: CosineWarmupScheduler(o, config.TRAIN.EPOCHS * steps, config.TRAIN.WARMUP_EPOCHS * steps, config.TRAIN.BASE_LR,
                                       config.TRAIN.MIN_LR, config.TRAIN.LR_SCHEDULER.WARMUP_PREFIX) for k, o in opts.items()}
     tr = Trainer(models, metrics, opts, config, device, loader, val_loader, sched, amp=config.AMP_ENABLE, gan=gan, logger=log,
-                 step_metrics=args.step_metrics)
+                 step_metrics=args.step_metrics, skip_nonfinite=args.skip_nonfinite, clip_grad=args.clip_grad)
     if gan and "msd" in config.TRAIN.ADVERSARIAL.DISCRIMINATORS and not args.no_graphs:
         log.info("DISCRIMINATORS lists 'msd': the step runs eagerly (no HIP graphs), as under --no-graphs")
     if graphs:

@@ -12,6 +12,11 @@
 //     p -= lr * wd * p;  m += (1 - b1) (g - m);  v = b2 v + (1 - b2) g g;
 //     p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // lr and t are read from DEVICE memory at run time (the schedule keeps working under graph replay).
+//
+// GUARD (vmasr_adamw_step_guarded): the same body behind the gradient guard's four device floats (csrc/gradnorm.hip): every gradient
+// element is multiplied by state[1] (the clip coefficient) as it is read — the gradient buffer is not modified —, and when state[2]
+// (found_inf) is set every workgroup returns before its first store: p, m, v and the shadows stay bit-identical.  The per-parameter
+// `step` counters advance by state[4] = 1 - found_inf in one small launch ahead of it (`step` then holds the count after this update).
 #include "common.h"
 
 namespace vmasr {
@@ -19,9 +24,15 @@ namespace {
 
 constexpr int kAdamChunk = 4096;   // elements per workgroup (256 threads x 4 float4)
 
+template <bool GUARD>
 __global__ __launch_bounds__(256) void adamw_kernel(const vmasr_adamw_item *__restrict__ items, const int2 *__restrict__ chunks,
                                                     const float *__restrict__ lr_p, const float *__restrict__ step_p, const float b1,
-                                                    const float b2, const float eps) {
+                                                    const float b2, const float eps, const float *__restrict__ guard) {
+    float clip = 1.f;
+    if constexpr (GUARD) {
+        if (guard[2] != 0.f) return;                          // a non-finite gradient somewhere: the step is not taken (uniform over the grid)
+        clip = guard[1];
+    }
     const int2 ck = chunks[blockIdx.x];                       // (item, chunk index within the item)
     const vmasr_adamw_item it = items[ck.x];
     const long base = (long)ck.y * kAdamChunk;
@@ -40,6 +51,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(const vmasr_adamw_item *__re
         lpt[(size_t)c * rows + r] = (bf16_t)P;
     };
     auto upd = [&](float &pp, float gg, float &mm, float &vv) {
+        if constexpr (GUARD) gg *= clip;
         pp *= decay;
         mm = fmaf(1.f - b1, gg - mm, mm);
         vv = fmaf(b2, vv, (1.f - b2) * gg * gg);
@@ -79,6 +91,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(const vmasr_adamw_item *__re
     }
 }
 
+// the per-parameter `step` counters of a guarded step: += guard[4] (1 - found_inf), one thread each, ahead of the update that reads them
+__global__ __launch_bounds__(256) void adamw_bump_kernel(float *const *__restrict__ steps, const int n, const float *__restrict__ guard) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) *steps[i] += guard[4];
+}
+
 }  // namespace
 }  // namespace vmasr
 
@@ -86,13 +104,31 @@ using namespace vmasr;
 
 VMASR_EXPORT int32_t vmasr_adamw_chunk(void) { return kAdamChunk; }
 
-VMASR_EXPORT int vmasr_adamw_step(const vmasr_adamw_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems,
-                                  const float *lr, const float *step, float beta1, float beta2, float eps, vmasr_stream_t stream) {
-    VMASR_REQUIRE(items && chunks && lr && step, VMASR_EINVAL, "adamw_step: null argument");
+template <bool GUARD>
+static int adamw_launch(const vmasr_adamw_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems, const float *lr,
+                        const float *step, float beta1, float beta2, float eps, const float *guard, vmasr_stream_t stream) {
+    VMASR_REQUIRE(items && chunks && lr && step && (!GUARD || guard), VMASR_EINVAL, "adamw_step: null argument");
     VMASR_REQUIRE(nchunks > 0 && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, VMASR_EINVAL,
                   "adamw_step: bad hyper-parameters");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    VMASR_LAUNCH(VMASR_K_ADAMW, 28.0 * (double)total_elems, adamw_kernel, dim3(nchunks), dim3(256), 0, st, items,
-                 reinterpret_cast<const int2 *>(chunks), lr, step, beta1, beta2, eps);
+    VMASR_LAUNCH(VMASR_K_ADAMW, 28.0 * (double)total_elems, adamw_kernel<GUARD>, dim3(nchunks), dim3(256), 0, st, items,
+                 reinterpret_cast<const int2 *>(chunks), lr, step, beta1, beta2, eps, guard);
     return check_launch("adamw_step");
+}
+
+VMASR_EXPORT int vmasr_adamw_step(const vmasr_adamw_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems,
+                                  const float *lr, const float *step, float beta1, float beta2, float eps, vmasr_stream_t stream) {
+    return adamw_launch<false>(items, chunks, nchunks, total_elems, lr, step, beta1, beta2, eps, nullptr, stream);
+}
+
+VMASR_EXPORT int vmasr_adamw_step_guarded(const vmasr_adamw_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems,
+                                          const float *lr, const float *step, float beta1, float beta2, float eps, const float *state,
+                                          float *const *step_counters, int32_t ncounters, vmasr_stream_t stream) {
+    VMASR_REQUIRE(state && ncounters >= 0 && (ncounters == 0 || step_counters), VMASR_EINVAL, "adamw_step_guarded: null argument");
+    if (ncounters > 0) {
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        VMASR_LAUNCH(VMASR_K_ADAMW, 8.0 * (double)ncounters, adamw_bump_kernel, dim3((ncounters + 255) / 256), dim3(256), 0, st, step_counters,
+                     ncounters, state);
+    }
+    return adamw_launch<true>(items, chunks, nchunks, total_elems, lr, step, beta1, beta2, eps, state, stream);
 }

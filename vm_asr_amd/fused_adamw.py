@@ -19,9 +19,13 @@ _ITEM = np.dtype([("p", "u8"), ("g", "u8"), ("m", "u8"), ("v", "u8"), ("lp", "u8
 class HipAdamWStep:
     """step() == optimizer.step() for a capturable torch.optim.AdamW (non-amsgrad, no maximize) whose parameters'
     `.grad` are fixed views (the trainer's flat gradient buffers).  `shadows`: {id(param): bf16 tensor} refreshed in
-    the same pass; `shadows_t`: {id(2-D param): bf16 tensor of the transposed shape}, likewise.  Raises ValueError if the optimiser does not qualify (the caller keeps optimizer.step())."""
+    the same pass; `shadows_t`: {id(2-D param): bf16 tensor of the transposed shape}, likewise.  Raises ValueError if the optimiser does not qualify (the caller keeps optimizer.step()).
+    `guard`: a grad_guard.GradGuard measured over the same gradients just before step(): the launch then scales every gradient element
+    by the guard's clip coefficient as it reads it, and takes no step at all — weights, moments, shadows and the `step` counters stay
+    bit-identical — when the guard found a non-finite element (what torch's fused AdamW does under a GradScaler), without a host read
+    (the counters advance by the guard's device value 1 - found_inf, in the same library call)."""
 
-    def __init__(self, optimizer, shadows=None, shadows_t=None):
+    def __init__(self, optimizer, shadows=None, shadows_t=None, guard=None):
         if not isinstance(optimizer, torch.optim.AdamW):
             raise ValueError("not an AdamW")
         groups = optimizer.param_groups
@@ -82,6 +86,12 @@ class HipAdamWStep:
         self.nchunks, self.total = len(chunks), sum(it[5] for it in items)
         self.steps, self._keep, self._ptrs = steps, keep, [it[:4] for it in items]
         self.optimizer = optimizer
+        self.guard = guard
+        if guard is not None:
+            if guard.state.device != dev or guard.state.dtype != torch.float32:
+                raise ValueError("the gradient guard's state is not an fp32 tensor on the optimiser's device")
+            # the step counters advance by the guard's state[4] = 1 - found_inf inside the guarded call: a table of their addresses
+            self._step_ptrs = torch.tensor([s_.data_ptr() for s_ in steps], dtype=torch.int64, device=dev)
 
     def still_valid(self):
         """The table holds raw pointers: it is stale once a parameter's .grad was re-bound (zero_grad(set_to_none), a new
@@ -100,6 +110,10 @@ class HipAdamWStep:
 
     @torch.no_grad()
     def step(self):
+        if self.guard is not None:
+            _lib.call(_lib.lib().vmasr_adamw_step_guarded, self.items, self.chunks, self.nchunks, self.total, self.lr, self.steps[0],
+                      self.betas[0], self.betas[1], self.eps, self.guard.state, self._step_ptrs, len(self.steps), device=self.lr.device)
+            return
         torch._foreach_add_(self.steps, 1)
         _lib.call(_lib.lib().vmasr_adamw_step, self.items, self.chunks, self.nchunks, self.total, self.lr, self.steps[0], self.betas[0],
                   self.betas[1], self.eps, device=self.lr.device)

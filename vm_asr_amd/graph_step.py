@@ -111,6 +111,9 @@ class GraphedTrainStep:
                 tr._reduce_and_step()
         cur.wait_stream(side)
         torch.cuda.synchronize()
+        if tr.grad_guards is not None and tr._hip_adamw_steps() is None:
+            raise RuntimeError("the gradient guard is on and the optimisers do not qualify for the HIP AdamW step: its "
+                               "optimizer.step() route reads found_inf on the host, which cannot be captured")
         for opt in [tr.optimizer_G] + ([tr.optimizer_D] if tr.gan else []):
             from .optim import lr_to_device
             if any(torch.is_tensor(g["lr"]) and not g["lr"].is_cuda for g in opt.param_groups):

@@ -303,7 +303,7 @@ class Trainer(BaseTrainer):
 
     def __init__(self, models, metric_ftns, optimizers, config, device, data_loader_train, data_loader_val=None,
                  lr_schedulers=None, amp=False, gan=False, logger=None, len_epoch=None, dp_mode="flat",
-                 amp_scope="generator", step_metrics=False):
+                 amp_scope="generator", step_metrics=False, skip_nonfinite=False, clip_grad=None):
         """dp_mode: "flat" = gradients live in one flat buffer per model and are all-reduced with ONE
         RCCL call per optimiser per step (also what makes the step HIP-graph capturable);
         "ddp" = torch DistributedDataParallel buckets overlapped with backward.
@@ -312,7 +312,14 @@ class Trainer(BaseTrainer):
         outside autocast, i.e. in fp32); "step" = generator, losses and discriminator (bf16 MPD).
         step_metrics: evaluate the metrics on EVERY step (and every validation batch) and average them over the epoch, as the
         reference does (trainer/trainer.py:158-182), through metric.Accumulator: one eager library call behind the step, no
-        host read until a line is printed / the epoch ends.  Off: the metrics are evaluated on the PRINT_FREQ steps only."""
+        host read until a line is printed / the epoch ends.  Off: the metrics are evaluated on the PRINT_FREQ steps only.
+        skip_nonfinite / clip_grad: the device-side gradient guard (grad_guard.GradGuard, csrc/gradnorm.hip), one per optimiser as the
+        reference has scaler_G and scaler_D (trainer/trainer.py:106-107): the generator's parameters under one, every listed
+        discriminator's under the other.  With either option an optimiser step whose gradients hold an inf or a NaN is not taken
+        (weights, Adam moments, step counters and bf16 shadows stay as they are); clip_grad (a float) also clips by global norm,
+        with torch.nn.utils.clip_grad_norm_'s coefficient.  The guard measures in _optimizer_steps(), i.e. AFTER the gradient
+        all-reduce has been waited for: on several ranks every rank sees the same averaged gradient and takes the same decision,
+        with no extra collective.  Both off (default): no guard object exists and no launch is added."""
         super().__init__(models, metric_ftns, optimizers, config, logger, resume_now=False)
         self.step_metrics = bool(step_metrics)
         self._metric_names = []
@@ -337,6 +344,11 @@ class Trainer(BaseTrainer):
         self._side = None                                     # _side_stream()
         self._warned_streamk = False                          # _two_streams()
         self._hip_adamw, self._hip_adamw_failed = None, False     # _hip_adamw_steps()
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.clip_grad = float(clip_grad) if clip_grad is not None else None
+        if self.clip_grad is not None and not self.clip_grad > 0:
+            raise ValueError(f"clip_grad={clip_grad!r}: expected a positive norm")
+        self.grad_guards = None                                   # _grad_guards(): [generator's, discriminators'] when the guard is on
         self._step_batch, self._lane_bwd_share = None, None   # enable_graphs(): the example batch's size, the chosen CU share
         self._graph_collectives = None                        # graph_collectives(): None = as VMASR_GRAPH_COLLECTIVES says
         self.graph_error, self.graph_variants = None, None    # enable_graphs()
@@ -368,6 +380,12 @@ class Trainer(BaseTrainer):
         for opt in (self.optimizer_G, self.optimizer_D):
             lr_to_device(opt, self.device)
         self._make_shadows()
+        if self.skip_nonfinite or self.clip_grad is not None:
+            from .grad_guard import GradGuard
+            # (the guards' device states exist from here on, so that enable_graphs() can undo its warm-up steps' counts; the pointer
+            #  tables are built at the first step, when the gradients exist)
+            self.grad_guards = [GradGuard([p for g in o.param_groups for p in g["params"]], self.device, self.clip_grad, params=True)
+                                for o in [self.optimizer_G] + ([self.optimizer_D] if self.gan else [])]
         if config.MODEL.RESUME_PATH is not None:
             self._resume_checkpoint()      # after .to(device): optimiser state lands next to the parameters
 
@@ -811,15 +829,64 @@ class Trainer(BaseTrainer):
         """AdamW for G (and D), then refresh the low-precision shadow weights (what graph B captures).
         With flat gradient buffers and capturable AdamW the update of each model is ONE launch of the HIP library
         (fused_adamw.HipAdamWStep: same state tensors, same arithmetic, bf16 shadows written in the same pass)."""
+        guards = self._grad_guards()
         fused = self._hip_adamw_steps()
         if fused is not None:
-            for f in fused:       # (the kernel also writes the bf16 shadow of every parameter it updates;
-                f.step()          #  parameters without a gradient do not change, their shadows stay valid)
+            for i, f in enumerate(fused):   # (the kernel also writes the bf16 shadow of every parameter it updates;
+                if guards is not None:      #  parameters without a gradient do not change, their shadows stay valid)
+                    guards[i].measure()     # no host read: the guarded launch reads the four floats on the device
+                f.step()
+            return
+        if guards is not None:
+            # optimizer.step() route (eager single-GPU step, MSD configurations, CPU, the first step that creates the state): clip in
+            # place, ONE host read of found_inf per optimiser, and no optimizer.step() / shadow refresh for a non-finite step
+            # (GradScaler's unfused route does the same)
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the gradient guard reads found_inf on the host on the optimizer.step() route: not capturable")
+            applied = False
+            for opt, guard in zip([self.optimizer_G] + ([self.optimizer_D] if self.gan else []), guards):
+                guard.measure()
+                if guard.found_inf():
+                    continue                # the gradients stay as they are
+                if self.clip_grad is not None:
+                    guard.clip_()
+                opt.step()
+                applied = True
+            if applied:
+                self._refresh_shadows()
             return
         self.optimizer_G.step()
         if self.gan:
             self.optimizer_D.step()
         self._refresh_shadows()
+
+    def _grad_guards(self):
+        """The gradient guards ([generator's, discriminators']) with pointer tables that match the parameters' current `.grad`s;
+        None when skip_nonfinite and clip_grad are both off."""
+        if self.grad_guards is None:
+            return None
+        for guard in self.grad_guards:
+            if not guard.still_valid():
+                guard.rebuild()
+        return self.grad_guards
+
+    def guard_report(self):
+        """{"grad_norm_G", "skipped_G"[, "grad_norm_D", "skipped_D"]} of the last step: one host read per guard; {} without guards."""
+        out = {}
+        for name, guard in zip("GD", self.grad_guards or []):
+            r = guard.read()
+            out[f"grad_norm_{name}"], out[f"skipped_{name}"] = r["grad_norm"], r["skipped"]
+        return out
+
+    def _save_checkpoint(self, epoch, save_best=False):
+        """As BaseTrainer's; with the gradient guard on, it is read once more first: a run in which NO step was ever applied (the last
+        one skipped, and as many skipped as there were steps) gets a warning.  What is saved does not change."""
+        for name, guard in zip("GD", (self.grad_guards or []) if self.rank == 0 else []):      # (rank 0 writes, rank 0 reads)
+            r = guard.read()
+            if r["found_inf"] and self.global_step > 0 and r["skipped"] >= self.global_step:
+                self.logger.warning(f"gradient guard {name}: all {r['skipped']} optimiser steps so far were skipped for non-finite "
+                                    "gradients; the checkpoint holds the weights the run started from")
+        super()._save_checkpoint(epoch, save_best)
 
     def _hip_adamw_steps(self):
         """The HipAdamWStep objects of this trainer's optimisers, built once the optimiser states exist (after the first
@@ -839,7 +906,8 @@ class Trainer(BaseTrainer):
             return None
         shadows = {id(src): dst for src, dst in zip(self._shadow_params, self._shadow_dst)}
         try:
-            built = [HipAdamWStep(o, shadows, self._shadow_t) for o in opts]
+            guards = self.grad_guards or [None] * len(opts)
+            built = [HipAdamWStep(o, shadows, self._shadow_t, guard=g) for o, g in zip(opts, guards)]
         except ValueError as e:
             if "not initialised" in str(e):
                 return None                       # first step: torch creates the state, the next call builds the table
@@ -921,6 +989,7 @@ class Trainer(BaseTrainer):
         for m in self.models.values():
             if m is not None:
                 tensors += [(t, t.detach().clone()) for t in list(unwrap(m).parameters()) + list(unwrap(m).buffers())]
+        tensors += [(g.state, g.state.clone()) for g in self.grad_guards or []]      # (enable_graphs' warm-up steps do not count)
         opt = []
         for o in [self.optimizer_G] + ([self.optimizer_D] if self.gan else []):
             for g in o.param_groups:
@@ -984,6 +1053,11 @@ class Trainer(BaseTrainer):
 
     def _enable_graphs(self, example_batch, warmup, preserve_state, first_replay):
         from .graph_step import GraphedTrainStep
+        if self.grad_guards is not None and not knobs.get("VMASR_HIP_ADAMW"):
+            # without the guarded AdamW launch the guard's decision is a host read (the optimizer.step() route): never captured
+            self.graph_error = "the gradient guard needs the HIP AdamW step (VMASR_HIP_ADAMW=1) to stay on the device"
+            self.logger.warning(f"HIP graph capture unavailable ({self.graph_error}): running eagerly")
+            return False
         snap = self._snapshot_training_state() if preserve_state else None
         multi = self.world > 1 and dist.is_initialized()
         if multi:
@@ -1164,8 +1238,9 @@ class Trainer(BaseTrainer):
                 if acc is not None:
                     vals.update(self._accumulated(acc, reset=False))    # shown: the running means over the steps so far
                 if self.rank == 0:
+                    vals.update(self.guard_report())                    # shown only: one read per guard, on these steps alone
                     self.logger.info(f"Epoch {epoch} [{batch_idx + 1}/{self.len_epoch}] " +
-                                     " ".join(f"{k}={v:.4f}" for k, v in vals.items()))
+                                     " ".join(f"{k}={v}" if isinstance(v, int) else f"{k}={v:.4f}" for k, v in vals.items()))
         # the learning-rate schedule advances once per EPOCH, with the reference's update index
         # (trainer/trainer.py:196-218: `(epoch * num_steps + batch_idx) // ACCUMULATION_STEPS` after the batch loop)
         if count:
