@@ -498,6 +498,32 @@ int vmasr_adamw_step_guarded(const vmasr_adamw_item *items, const int32_t *chunk
                              const float *step, float beta1, float beta2, float eps, const float *state, float *const *step_counters,
                              int32_t ncounters, vmasr_stream_t stream);
 
+/* SGD step of many parameter tensors in one launch (csrc/sgd.hip; torch.optim.SGD with dampening 0 and maximize off, as
+ * utils/optimizer.py:32-39 of the reference configures it): g' = g + wd p; buf = momentum buf + g'; p -= lr (nesterov ? g' + momentum buf
+ * : buf), fp32.  `items` is a DEVICE array, one entry per tensor; `chunks` the DEVICE table of (item index, chunk index) int32 pairs that
+ * vmasr_adamw_step takes, one per workgroup, chunk = vmasr_adamw_chunk() elements; total_elems = sum of n.  lr is a DEVICE scalar read at
+ * run time; 0 <= momentum < 1.  buf must exist: a zero buffer gives what torch's first step (buf = g') gives.  lp / lpt (may be NULL):
+ * bf16 copy of the updated parameter / of the updated 2-D parameter transposed, written in the same pass as by vmasr_adamw_step.
+ * vec: set when p, g, buf are 16-byte and lp 8-byte aligned.  No float atomics: the same inputs give the same bits on every call. */
+typedef struct vmasr_sgd_item {
+    float *p;
+    const float *g;
+    float *buf;           /* momentum buffer */
+    void *lp;
+    void *lpt;            /* lpt[c * rows + r] = p[r * cols + c] */
+    int64_t n;
+    float weight_decay;
+    int32_t vec;
+    int32_t rows, cols;
+} vmasr_sgd_item;
+int vmasr_sgd_step(const vmasr_sgd_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems, const float *lr, float momentum,
+                   int32_t nesterov, vmasr_stream_t stream);
+/* The same behind the gradient guard's `state` (vmasr_grad_norm), read as vmasr_adamw_step_guarded reads it: every gradient element is
+ * multiplied by state[1] as it is read (the gradient buffer is left as it is); when state[2] != 0 nothing is written: p, buf and the
+ * shadows stay bit-identical.  SGD has no step counters, so this is one launch. */
+int vmasr_sgd_step_guarded(const vmasr_sgd_item *items, const int32_t *chunks, int32_t nchunks, int64_t total_elems, const float *lr,
+                           float momentum, int32_t nesterov, const float *state, vmasr_stream_t stream);
+
 /* Spectrally normalised weights of one discriminator layer, stacked for the batched pass (model/discriminator.py:26-45:
  * spectral_norm around every convolution; sigma, u, v from the power iteration are constants for autograd):
  *   fwd: out (n, N, k*Cin) with out[s, o, j*Cin + c] = W_s[o, c, j] / sigma_s   (W_s: (N, Cin, k) fp32, HOST array of n pointers)
@@ -945,6 +971,7 @@ enum {
     VMASR_K_DCONV1D_WGRAD,      /* its weight / bias gradient: whole-K tiles, or (b, t) slabs into a workspace */
     VMASR_K_DCONV1D_WGRAD_REDUCE, /* the ordered sum of those slabs */
     VMASR_K_GRAD_NORM,          /* gradient guard: per-chunk sums of squares + non-finite flags, ordered finish (csrc/gradnorm.hip) */
+    VMASR_K_SGD,                /* SGD / Nesterov step of all parameters (+ bf16 shadow refresh), one launch (csrc/sgd.hip) */
     VMASR_K_RESAMPLE,           /* polyphase FIR resampling of a batch of rows (csrc/resample.hip) */
     VMASR_K_COUNT
 };

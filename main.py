@@ -89,7 +89,7 @@ def use_graphs(args, config):
 
 def main(args, config):
     import vm_asr_amd
-    from vm_asr_amd.trainer import (CosineWarmupScheduler, SyntheticVCTK, Trainer, _Logger, build_optimizer, default_metric_ftns,
+    from vm_asr_amd.trainer import (SyntheticVCTK, Trainer, _Logger, build_optimizer, build_scheduler, default_metric_ftns,
                                     init_distributed)
     log = _Logger()
     if config.INFERENCE_MODE and not args.input:
@@ -147,8 +147,7 @@ def main(args, config):
     if gan:
         opts["discriminator"] = build_optimizer(config, [models[d] for d in config.TRAIN.ADVERSARIAL.DISCRIMINATORS], capturable=graphs)
     steps = max(1, len(loader) // config.TRAIN.ACCUMULATION_STEPS)
-    sched = {k: CosineWarmupScheduler(o, config.TRAIN.EPOCHS * steps, config.TRAIN.WARMUP_EPOCHS * steps, config.TRAIN.BASE_LR,
-                                      config.TRAIN.MIN_LR, config.TRAIN.LR_SCHEDULER.WARMUP_PREFIX) for k, o in opts.items()}
+    sched = {k: build_scheduler(config, o, steps) for k, o in opts.items()}      # TRAIN.LR_SCHEDULER.NAME: cosine | linear | step | multistep
     tr = Trainer(models, metrics, opts, config, device, loader, val_loader, sched, amp=config.AMP_ENABLE, gan=gan, logger=log,
                  step_metrics=args.step_metrics, skip_nonfinite=args.skip_nonfinite, clip_grad=args.clip_grad)
     if gan and "msd" in config.TRAIN.ADVERSARIAL.DISCRIMINATORS and not args.no_graphs:

@@ -142,6 +142,8 @@ SYMBOLS = {
     "vmasr_adamw_chunk": (c_i32, []),
     "vmasr_adamw_step": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp]),
     "vmasr_adamw_step_guarded": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_i32, c_vp]),
+    "vmasr_sgd_step": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, ctypes.c_float, c_i32, c_vp]),
+    "vmasr_sgd_step_guarded": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, ctypes.c_float, c_i32, c_vp, c_vp]),
     "vmasr_grad_norm_workspace": (c_sz, [c_i32]),
     "vmasr_grad_norm": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i64, ctypes.c_float, c_vp, c_vp, c_sz, c_vp]),
     "vmasr_masked_l1_blocks": (c_i32, []),
@@ -373,7 +375,7 @@ def rows2d(t, width):
     return t2 if t2.is_contiguous() else t2.contiguous()
 
 
-K_COUNT = 81
+K_COUNT = 82
 
 
 def zeros_f32(device, *shapes):

@@ -41,7 +41,7 @@ const char *kNames[VMASR_K_COUNT] = {
     "conv_mfma_fwd", "conv_mfma_dgrad", "conv_mfma_wgrad", "wgrad_finish", "skinny_linear", "metrics", "resample_design", "degrade_batch",
     "gconv1d_fwd", "gconv1d_dgrad", "gconv1d_wgrad", "gconv1d_wgrad_reduce",
     "stem1d_fwd", "stem1d_bwd", "stem1d_bwd_reduce",
-    "dconv1d_fwd", "dconv1d_dgrad", "dconv1d_reduce", "dconv1d_wgrad", "dconv1d_wgrad_reduce", "grad_norm", "resample_poly"};
+    "dconv1d_fwd", "dconv1d_dgrad", "dconv1d_reduce", "dconv1d_wgrad", "dconv1d_wgrad_reduce", "grad_norm", "sgd", "resample_poly"};
 }  // namespace
 
 bool g_prof_on = false;

@@ -14,7 +14,8 @@ Two-stream layout (default on the GPU: trainer._two_streams) — TWO graphs:
               world_size > 1: both all-reduces run between graph A and graph B on torch.distributed's communicator (default).
               VMASR_GRAPH_COLLECTIVES=1 (RCCL, opt-in): the MPD gradient's all-reduce is a THIRD branch of graph A, issued on the side
               stream right behind the D loss' backward; the generator's (9 MB) follows its pack; both join at the end of the graph.
-    graph B   AdamW step for G and for D (capturable optimisers) + refresh of the bf16 shadow weights
+    graph B   AdamW step for G and for D (capturable optimisers) + refresh of the bf16 shadow weights; TRAIN.OPTIMIZER.NAME sgd: the
+              one-launch HIP SGD step (fused_sgd.HipSgdStep) — torch's SGD is never captured, it reads the learning rate on the host
 
 One-stream layout (VMASR_TWO_STREAM=0, deterministic mode, no shared fake pass) — three graphs:
 
@@ -34,9 +35,14 @@ graph A like any ATen kernel; the in-library event profiler must be off during c
 """
 import torch
 
-__all__ = ["GraphedTrainStep", "replay_selftest"]
+__all__ = ["GraphedTrainStep", "SgdNotCapturable", "replay_selftest"]
 
 _SELFTEST = {}
+
+
+class SgdNotCapturable(RuntimeError):
+    """An SGD optimiser whose step would have to be captured as torch's own: Trainer.enable_graphs() raises it on, where every
+    other capture failure means an eager run with a warning."""
 
 
 def replay_selftest(device):
@@ -88,8 +94,10 @@ class GraphedTrainStep:
             raise RuntimeError("graph capture needs TRAIN.ACCUMULATION_STEPS == 1")
         if tr.dp_mode != "flat":
             raise RuntimeError("graph capture needs dp_mode='flat' (DDP hooks are not capturable here)")
-        for opt in [tr.optimizer_G] + ([tr.optimizer_D] if tr.gan else []):
-            if not opt.defaults.get("capturable", False):
+        opts = [tr.optimizer_G] + ([tr.optimizer_D] if tr.gan else [])
+        tr._check_sgd_capturable()      # an SGD is admitted when, and only when, its one-launch HIP step can be built
+        for opt in opts:
+            if not isinstance(opt, torch.optim.SGD) and not opt.defaults.get("capturable", False):
                 raise RuntimeError("graph capture needs capturable=True optimisers (build_optimizer(..., capturable=True))")
         if not replay_selftest(tr.device):
             raise RuntimeError("this HIP runtime does not replay captured graphs faithfully (memset nodes lose their order: "
@@ -111,7 +119,12 @@ class GraphedTrainStep:
                 tr._reduce_and_step()
         cur.wait_stream(side)
         torch.cuda.synchronize()
-        if tr.grad_guards is not None and tr._hip_adamw_steps() is None:
+        if tr._sgd() and tr._hip_sgd_steps() is None:
+            # torch's SGD would be what graph B captures: it reads the lr tensor with .item(), the replay would keep that value for ever
+            raise SgdNotCapturable("the SGD optimisers do not qualify for the one-launch HIP step "
+                                   f"({tr._hip_step_error or 'no flat gradient buffers'}), and torch's SGD is never captured: it reads "
+                                   "the learning rate on the host")
+        if tr.grad_guards is not None and tr._hip_optimizer_steps() is None:
             raise RuntimeError("the gradient guard is on and the optimisers do not qualify for the HIP AdamW step: its "
                                "optimizer.step() route reads found_inf on the host, which cannot be captured")
         for opt in [tr.optimizer_G] + ([tr.optimizer_D] if tr.gan else []):

@@ -4,7 +4,7 @@
 outside the declared set raises ValueError at the read.  Nothing else under vm_asr_amd/ reads a VMASR_* variable.  Readers:
 "python" = this package through get(), for the switches that existed when this registry was written: tests/test_knobs.py pins exactly
 that set and its defaults in a fixed table.  A python-read switch added later cannot join the table, so it carries "python:<feature>"
-(so far "python:msd", "python:gmlp") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py, tests/test_msd_tail.py, tests/test_gmlp.py);
+(so far "python:msd", "python:gmlp", "python:sgd") and the tests of its feature check its default, its values and the ValueError of a bad one (tests/test_msd.py, tests/test_msd_stem.py, tests/test_msd_tail.py, tests/test_gmlp.py, tests/test_lr_schedules.py);
 "csrc" = a static `getenv` in vm_asr_amd/csrc (read once per process; listed here with the
 default the C++ code applies); "external" = bench.py, the tests, tools/ or oracle/, which read their own names directly.
 No torch import: tests/test_knobs.py and tools load this module without a GPU stack.
@@ -163,6 +163,8 @@ KNOBS = {k.name: k for k in (
     _k("VMASR_LN_DEFER", "flag", 1, "LayerNorm's dgamma / dbeta of a whole backward pass reduced in one launch"),
     _k("VMASR_HIP_ADAMW", "flag", 1, "the multi-tensor AdamW kernel on the flat gradient buffers"),
     _k("VMASR_FUSED_ADAMW", "flag", 1, "torch's fused AdamW where the HIP kernel does not apply"),
+    _k("VMASR_HIP_SGD", "flag", 1, "the multi-tensor SGD kernel on the flat gradient buffers (TRAIN.OPTIMIZER.NAME sgd; fused_sgd.py); 0 = "
+       "optimizer.step(), which graph capture refuses", reader="python:sgd"),
     _k("VMASR_LP_SHADOWS", "flag", 1, "bf16 shadow copies of the parameters, refreshed by the optimiser kernel"),
     _k("VMASR_LP_SHADOWS_T", "flag", 1, "transposed bf16 shadows of the 2-D weights too"),
     _k("VMASR_RESUME_CONFIG_MISMATCH", "choice", "raise", "a checkpoint written under another configuration: raise or warn", values=("raise", "warn")),

@@ -39,10 +39,10 @@ from . import metric as metric_mod
 from .data import SyntheticVCTK
 from .grad_sync import FlatGrads
 from .loss import HiFiGANLoss, MultiResolutionSTFTLoss, mae_loss, mse_loss
-from .optim import (_RUNTIME_GROUP_KEYS, CosineWarmupScheduler, build_optimizer, load_optimizer_state, lr_to_device,  # noqa: F401
-                    portable_optimizer_state, set_weight_decay, unwrap)
+from .optim import (_RUNTIME_GROUP_KEYS, CosineWarmupScheduler, build_optimizer, build_scheduler, load_optimizer_state,  # noqa: F401
+                    lr_to_device, portable_optimizer_state, set_weight_decay, unwrap)
 
-__all__ = ["BaseTrainer", "Trainer", "SyntheticVCTK", "CosineWarmupScheduler", "build_optimizer",
+__all__ = ["BaseTrainer", "Trainer", "SyntheticVCTK", "CosineWarmupScheduler", "build_optimizer", "build_scheduler",
            "set_weight_decay", "init_distributed", "unwrap"]
 
 
@@ -344,6 +344,8 @@ class Trainer(BaseTrainer):
         self._side = None                                     # _side_stream()
         self._warned_streamk = False                          # _two_streams()
         self._hip_adamw, self._hip_adamw_failed = None, False     # _hip_adamw_steps()
+        self._hip_sgd, self._hip_sgd_failed = None, False         # _hip_sgd_steps()
+        self._hip_step_error = None                               # why the last one-launch table could not be built
         self.skip_nonfinite = bool(skip_nonfinite)
         self.clip_grad = float(clip_grad) if clip_grad is not None else None
         if self.clip_grad is not None and not self.clip_grad > 0:
@@ -826,11 +828,11 @@ class Trainer(BaseTrainer):
         return ctx()
 
     def _optimizer_steps(self):
-        """AdamW for G (and D), then refresh the low-precision shadow weights (what graph B captures).
-        With flat gradient buffers and capturable AdamW the update of each model is ONE launch of the HIP library
-        (fused_adamw.HipAdamWStep: same state tensors, same arithmetic, bf16 shadows written in the same pass)."""
+        """AdamW (or SGD) for G (and D), then refresh the low-precision shadow weights (what graph B captures).
+        With flat gradient buffers and capturable optimisers the update of each model is ONE launch of the HIP library
+        (fused_adamw.HipAdamWStep / fused_sgd.HipSgdStep: same state tensors, same arithmetic, bf16 shadows written in the same pass)."""
         guards = self._grad_guards()
-        fused = self._hip_adamw_steps()
+        fused = self._hip_optimizer_steps()
         if fused is not None:
             for i, f in enumerate(fused):   # (the kernel also writes the bf16 shadow of every parameter it updates;
                 if guards is not None:      #  parameters without a gradient do not change, their shadows stay valid)
@@ -891,14 +893,33 @@ class Trainer(BaseTrainer):
     def _hip_adamw_steps(self):
         """The HipAdamWStep objects of this trainer's optimisers, built once the optimiser states exist (after the first
         torch step) and the gradients live in the flat buffers; None -> use optimizer.step()."""
-        if self.device.type != "cuda" or self.dp_mode != "flat" or not knobs.get("VMASR_HIP_ADAMW"):
+        from .fused_adamw import HipAdamWStep
+        return self._hip_steps("_hip_adamw", "VMASR_HIP_ADAMW", HipAdamWStep)
+
+    def _hip_sgd_steps(self):
+        """The same for torch.optim.SGD (fused_sgd.HipSgdStep).  That class creates the momentum buffers it misses, so the table
+        exists from the first step on: nothing torch's SGD would have to run first."""
+        from .fused_sgd import HipSgdStep
+        return self._hip_steps("_hip_sgd", "VMASR_HIP_SGD", HipSgdStep)
+
+    def _hip_optimizer_steps(self):
+        """The one-launch step objects of whichever kind this trainer's optimisers are; None -> use optimizer.step()."""
+        return self._hip_sgd_steps() if self._sgd() else self._hip_adamw_steps()
+
+    def _sgd(self):
+        """Is an optimiser of this trainer a torch.optim.SGD (TRAIN.OPTIMIZER.NAME sgd)?"""
+        return any(isinstance(o, torch.optim.SGD) for o in (self.optimizer_G, self.optimizer_D))
+
+    def _hip_steps(self, attr, knob, cls):
+        """One `cls` object per optimiser, kept in `attr` while their pointer tables are valid.  A refusal other than "state not there
+        yet" is final for this trainer (`attr`_failed); `_hip_step_error` keeps its reason."""
+        if self.device.type != "cuda" or self.dp_mode != "flat" or not knobs.get(knob):
             return None
-        cur = self._hip_adamw
+        cur = getattr(self, attr)
         if cur is not None and all(f.still_valid() for f in cur):
             return cur
-        if self._hip_adamw_failed:
+        if getattr(self, attr + "_failed"):
             return None
-        from .fused_adamw import HipAdamWStep
         # every model whose parameters the two optimisers hold needs its flat buffer (the D optimiser holds every listed discriminator)
         d_keys = self._d_keys()
         opts = [self.optimizer_G] + ([self.optimizer_D] if self.gan else [])
@@ -907,13 +928,14 @@ class Trainer(BaseTrainer):
         shadows = {id(src): dst for src, dst in zip(self._shadow_params, self._shadow_dst)}
         try:
             guards = self.grad_guards or [None] * len(opts)
-            built = [HipAdamWStep(o, shadows, self._shadow_t, guard=g) for o, g in zip(opts, guards)]
+            built = [cls(o, shadows, self._shadow_t, guard=g) for o, g in zip(opts, guards)]
         except ValueError as e:
             if "not initialised" in str(e):
                 return None                       # first step: torch creates the state, the next call builds the table
-            self._hip_adamw_failed = True
+            setattr(self, attr + "_failed", True)
+            self._hip_step_error = f"{cls.__name__}: {e}"
             return None
-        self._hip_adamw = built
+        setattr(self, attr, built)
         return built
 
     def _reduce_and_step(self):
@@ -1035,6 +1057,7 @@ class Trainer(BaseTrainer):
         if self._msd:      # before anything is captured or allocated
             raise NotImplementedError("enable_graphs: the step with the multi-scale discriminator (MSD) is eager only; "
                                       "graph capture covers the generator and ['mpd'] configurations")
+        self._check_sgd_capturable()
         import gc as _gc
         guard = _gc.isenabled() and knobs.get("VMASR_GRAPH_GC_GUARD")
         if guard:
@@ -1051,9 +1074,31 @@ class Trainer(BaseTrainer):
                     torch.cuda.synchronize(self.device)
                 _gc.enable()
 
+    def _check_sgd_capturable(self):
+        """An SGD optimiser is captured through fused_sgd.HipSgdStep or not at all: torch's SGD reads a tensor lr with .item(), so a
+        captured optimizer.step() would replay the learning rate of the capture for ever.  Raises RuntimeError with the reason,
+        before anything is captured or allocated (what needs gradients is checked again by graph_step after its warm-up steps)."""
+        if not self._sgd():
+            return
+        why = None
+        if not knobs.get("VMASR_HIP_SGD"):
+            why = "VMASR_HIP_SGD=0 selects optimizer.step()"
+        elif self.device.type != "cuda" or self.dp_mode != "flat":
+            why = "the HIP SGD step needs a GPU and dp_mode='flat'"
+        else:
+            from .fused_sgd import HipSgdStep
+            try:
+                for o in [self.optimizer_G] + ([self.optimizer_D] if self.gan else []):
+                    HipSgdStep.check(o)
+            except ValueError as e:
+                why = f"HipSgdStep: {e}"
+        if why is not None:
+            raise RuntimeError(f"enable_graphs: TRAIN.OPTIMIZER.NAME sgd is captured with the one-launch HIP step only, and {why}; "
+                               "torch's SGD reads the learning rate on the host, which a capture would freeze (run with --no-graphs)")
+
     def _enable_graphs(self, example_batch, warmup, preserve_state, first_replay):
-        from .graph_step import GraphedTrainStep
-        if self.grad_guards is not None and not knobs.get("VMASR_HIP_ADAMW"):
+        from .graph_step import GraphedTrainStep, SgdNotCapturable
+        if self.grad_guards is not None and not self._sgd() and not knobs.get("VMASR_HIP_ADAMW"):
             # without the guarded AdamW launch the guard's decision is a host read (the optimizer.step() route): never captured
             self.graph_error = "the gradient guard needs the HIP AdamW step (VMASR_HIP_ADAMW=1) to stay on the device"
             self.logger.warning(f"HIP graph capture unavailable ({self.graph_error}): running eagerly")
@@ -1099,6 +1144,8 @@ class Trainer(BaseTrainer):
         def label(variant):
             return "one_generator_stream_ms" if not variant[0] else ("phase_lane_ms" if variant[1] is None else f"phase_lane_d_bwd_{variant[1]:.3f}_ms")
 
+        sgd_refused = []
+
         def attempt():
             try:
                 self._graphed = GraphedTrainStep(self, example_batch, warmup)
@@ -1108,6 +1155,8 @@ class Trainer(BaseTrainer):
                 self.graph_error = f"{type(e).__name__}: {e}"
                 self.logger.warning(f"HIP graph capture unavailable ({self.graph_error})")
                 ok = False
+                if isinstance(e, SgdNotCapturable):
+                    sgd_refused.append(str(e))      # not a reason to train eagerly without a word: raised below, state restored
             if multi:
                 # all ranks replay graphs or none does: a rank that fell back to the eager step would issue its collectives in a
                 # different order relative to its kernels and run ~2x slower — the others would sit in the all-reduce
@@ -1182,6 +1231,8 @@ class Trainer(BaseTrainer):
         if snap is not None:
             torch.cuda.synchronize(self.device)
             self._restore_training_state(snap)
+        if not ok and sgd_refused:
+            raise RuntimeError(f"enable_graphs: {sgd_refused[-1]}")
         return ok
 
     def graph_collectives(self):
